@@ -16,6 +16,16 @@ epoch on CPU/gloo = 51.0 images/sec; `vs_baseline` =
 our aggregate images/sec ÷ 51.0.
 
 Usage: python bench.py --gpus N --steps K --warmup W
+           [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times exactly K steps and prints one JSON
+line.  ``--dump-outputs DIR`` then also writes DIR/<name>.npy: the state is
+rewound to its seeded initial value and the last timed step is run again
+through the timed path (same captured graph, same batch); ``loss`` and
+``bn_running_stats`` are what that step computed.  ``det_*`` are the same
+step recomputed with fixed-order reductions, gradient included (``--infer``:
+the last timed step's own ``logits_sum``).  See docs/BENCH.md.
+``--full`` is where measurements beyond the headline figure belong; today
+there are none.
 (N>1 is launched by the driver via torch.distributed.run, one rank per GPU;
 standalone multi-GPU invocation re-execs torchrun itself.)
 """
@@ -44,7 +54,78 @@ def parse_args():
                     help="disable hipGraph capture (eager fallback)")
     ap.add_argument("--infer", action="store_true",
                     help="serving mode: eval-only forward throughput")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, rerun the last timed step "
+                         "from the seeded initial state and write what it "
+                         "computed to DIR/<name>.npy (float32; det_* files: "
+                         "the same step with fixed-order reductions; see "
+                         "docs/BENCH.md)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extended measurements that are not "
+                         "needed for the headline figure (none exist yet: "
+                         "the other configurations are separate commands, "
+                         "see docs/BENCH.md)")
     return ap.parse_args()
+
+
+# --dump-outputs: 64 MB in all; one large array (the flat gradient) gets
+# most of it, the others are tiny
+DUMP_ARRAY_BUDGET_BYTES = 48 << 20
+
+
+def state_tensors(mgr, opt, model):
+    """Every tensor a training step updates in place: flat master / grad /
+    bf16 shadow / RSCK images / BN-stats arena, the optimizer's buffers and
+    the model's BN buffers."""
+    import torch
+    ts = [mgr.master, mgr.grad, mgr.shadow, mgr.rsck, mgr.stats_arena]
+    ts += [v for v in vars(opt).values() if isinstance(v, torch.Tensor)]
+    ts += [b for b in model.buffers() if b.numel() > 0]
+    return ts
+
+
+def rewind(tensors, snapshot):
+    import torch
+    with torch.no_grad():
+        for t, s in zip(tensors, snapshot):
+            t.copy_(s)
+
+
+def first_moment(opt):
+    """The optimizer's flat first-moment buffer; after ONE step from zeroed
+    state it is the step's whole gradient (HorizonAdam: (1-beta1)*g,
+    HorizonSGD: g)."""
+    buf = opt.m if hasattr(opt, "m") else opt.mom
+    if buf is None:
+        raise ValueError("SGD without momentum keeps no gradient buffer "
+                         "for --dump-outputs to write")
+    return buf
+
+
+def bn_running_stats(model):
+    """Every BN running mean/var, concatenated in module order."""
+    import torch
+    return torch.cat([b.detach().flatten().float()
+                      for n, b in model.named_buffers()
+                      if n.endswith(("running_mean", "running_var"))])
+
+
+def write_arrays(out_dir, arrays):
+    """Write {name: tensor} as float32 out_dir/<name>.npy.  An array over
+    the budget is cut to a fixed seeded sample, in buffer order."""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    keep = DUMP_ARRAY_BUDGET_BYTES // 4
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > keep:
+            gen = torch.Generator().manual_seed(1234)
+            idx = torch.randperm(t.numel(), generator=gen)[:keep]
+            t = t[idx.sort().values.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.to(torch.float32).cpu().numpy())
 
 
 def maybe_reexec_torchrun(args):
@@ -108,6 +189,9 @@ def main():
     comm_buf = (torch.zeros_like(mgr.grad, dtype=torch.bfloat16)
                 if use_comm else None)
     inv_world = 1.0 / world
+    # --dump-outputs: keep the seeded initial state to rewind to (below)
+    state0 = ([t.clone() for t in state_tensors(mgr, opt, model)]
+              if args.dump_outputs and not args.infer else None)
 
     # Overlapped bucketed all-reduce (default at world>1): the flat grad is
     # reduced in reverse-layer buckets launched DURING backward (per-unit
@@ -200,8 +284,8 @@ def main():
     def run_step(i):
         if graphs is not None:
             graphs[i % pool_n].replay()
-        else:
-            train_step(pool_x[i % pool_n], pool_y[i % pool_n])
+            return losses_static[i % pool_n]
+        return train_step(pool_x[i % pool_n], pool_y[i % pool_n])
 
     for i in range(args.warmup):
         run_step(i)
@@ -210,8 +294,9 @@ def main():
         dist.barrier(device_ids=[local_rank])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    step_out = None
     for i in range(args.steps):
-        run_step(i)
+        step_out = run_step(i)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier(device_ids=[local_rank])
@@ -226,6 +311,44 @@ def main():
     else:
         final_loss = float(train_step(pool_x[0], pool_y[0])
                            .detach().float().cpu())
+
+    if args.dump_outputs and step_out is not None:
+        arrays = {}
+        if args.infer:
+            # eval forward has no atomics: bitwise repeatable as it is
+            arrays["logits_sum"] = step_out
+        else:
+            # What the W + K timed steps leave is no yardstick: run to run,
+            # ONE fast step from identical state already differs at the
+            # bf16 rounding level in its forward outputs and by ~25% rms in
+            # its gradient (f32-atomic order noise, amplified layer by
+            # layer on the way back: profiles/bench_dump_noise.txt), and
+            # training compounds that.  So every rank rewinds to the seeded
+            # initial state and runs the last timed step again, through the
+            # timed path itself (same captured graph, same batch).  Its
+            # forward outputs are written; its gradient is not, being noise
+            # to a quarter.
+            tensors = state_tensors(mgr, opt, model)
+            rewind(tensors, state0)
+            arrays["loss"] = run_step(args.steps - 1).clone()
+            torch.cuda.synchronize()
+            arrays["bn_running_stats"] = bn_running_stats(model)
+            # The same step once more from the same state, eagerly, with the
+            # kernels' fixed-order reductions (bitwise repeatable, ~8x the
+            # step time): the det_* files, gradient included.  They show the
+            # deterministic variants of the reductions, not the timed ones.
+            rewind(tensors, state0)
+            ext = _ops.extension()
+            was_det = ext.deterministic_enabled()
+            ext.set_deterministic(True)
+            j = (args.steps - 1) % pool_n
+            arrays["det_loss"] = train_step(pool_x[j], pool_y[j])
+            torch.cuda.synchronize()
+            ext.set_deterministic(was_det)
+            arrays["det_bn_running_stats"] = bn_running_stats(model)
+            arrays["det_opt_first_moment"] = first_moment(opt)
+        if rank == 0:
+            write_arrays(args.dump_outputs, arrays)
 
     if rank == 0:
         out = build_record(
