@@ -84,6 +84,19 @@ void launch_grad_divergence(const float*, float*, float*, float*, long, int,
                             hipStream_t);
 void launch_normalize_u8(const void*, void*, long, int, long, float, float,
                          hipStream_t);
+void set_kernels_bn_owner(int);
+int kernels_bn_owner();
+void bn_owner_launch_counts(long*, long*);
+int bn_owner_fwd_pick(long, int, int);
+int bn_owner_bwd_pick(long, int, int);
+void launch_bn_fwd_owner(const float*, const void*, void*, void*,
+                         const float*, const float*, float*, float*, float*,
+                         float*, long, int, float, float, int, int, int,
+                         hipStream_t);
+void launch_bn_bwd_owner(const void*, const void*, const void*, const float*,
+                         const float*, const float*, const float*, float*,
+                         float*, void*, void*, long, int, int, int,
+                         hipStream_t);
 }
 
 namespace {
@@ -104,6 +117,18 @@ void set_deterministic(bool on) {
   set_kernels_deterministic(on ? 1 : 0);
 }
 bool deterministic_enabled() { return g_deterministic; }
+
+// Channel-owner BatchNorm (single-launch reduce+apply at small M): runtime
+// switch so one process can run both dispatches (tests, A/B timing).
+// Deterministic mode always keeps the two-kernel dispatch.
+void set_bn_owner(bool on) { set_kernels_bn_owner(on ? 1 : 0); }
+bool bn_owner_enabled() { return kernels_bn_owner() != 0; }
+// (forward, backward) owner-kernel launches so far in this process.
+std::vector<int64_t> bn_owner_launches() {
+  long f = 0, b = 0;
+  bn_owner_launch_counts(&f, &b);
+  return {(int64_t)f, (int64_t)b};
+}
 
 // ---- deferred (batched) wgrad ---------------------------------------------
 // The weight-gradient GEMMs are off the backward's critical chain (nothing
@@ -411,11 +436,8 @@ std::vector<Tensor> conv_bn_act_fwd(
   Tensor stats, smean, sinvstd;
   float* stats_ptr = nullptr;
   if (training) {
-    // stats_buf (manager arena) arrives pre-zeroed by the fused optimizer
-    stats = stats_buf.has_value() ? *stats_buf : at::zeros({2L * K}, fopt);
     smean = at::empty({K}, fopt);
     sinvstd = at::empty({K}, fopt);
-    stats_ptr = stats.data_ptr<float>();
   } else {
     smean = at::empty({0}, fopt);
     sinvstd = at::empty({0}, fopt);
@@ -427,6 +449,14 @@ std::vector<Tensor> conv_bn_act_fwd(
   }
   auto st = cur_stream();
   int splitk = conv_fwd_splitk(p);
+  // the owner kernel keeps its sums in the workgroup: no stats buffer
+  const int own = (training && splitk > 1)
+                      ? bn_owner_fwd_pick((long)p.M, K, 0) : 0;
+  if (training && !own) {
+    // stats_buf (manager arena) arrives pre-zeroed by the fused optimizer
+    stats = stats_buf.has_value() ? *stats_buf : at::zeros({2L * K}, fopt);
+    stats_ptr = stats.data_ptr<float>();
+  }
   if (splitk > 1) {
     int kchunk = ((p.Kd + splitk - 1) / splitk + 31) / 32 * 32;
     splitk = (p.Kd + kchunk - 1) / kchunk;
@@ -435,6 +465,19 @@ std::vector<Tensor> conv_bn_act_fwd(
     Tensor ws = at::empty({(long)splitk * p.M * K}, fopt);
     launch_conv_fwd_splitk(x.data_ptr(), w.data_ptr(), ws.data_ptr<float>(),
                            p, splitk, st);
+    if (own) {
+      // one workgroup per channel slice reduces and applies: no stats
+      // arena, no atomics, one slab pass
+      launch_bn_fwd_owner(ws.data_ptr<float>(), res_ptr, y.data_ptr(),
+                          convout.data_ptr(), gamma.data_ptr<float>(),
+                          beta.data_ptr<float>(),
+                          running_mean.data_ptr<float>(),
+                          running_var.data_ptr<float>(),
+                          smean.data_ptr<float>(), sinvstd.data_ptr<float>(),
+                          (long)p.M, K, (float)momentum, (float)eps,
+                          (int)act, splitk, own, st);
+      return {y, convout, smean, sinvstd};
+    }
     if (training)
       launch_stats_reduce(ws.data_ptr<float>(), stats_ptr, (long)p.M, K,
                           splitk, st);
@@ -500,19 +543,23 @@ std::vector<Tensor> conv_bn_act_bwd(
   int mask_mode = act == 1 ? (has_res ? 1 : 2)
                  : act == 2 ? (has_res ? 3 : 4) : 0;
   Tensor sum_dz, sum_dzx;
+  const int own = sums_ready ? 0 : bn_owner_bwd_pick((long)p.M, K, 0);
   if (sums_ready) {  // computed by the downstream conv's dx producer
     sum_dz = direct ? *dbeta_out : *sum_dz_in;
     sum_dzx = direct ? *dgamma_out : *sum_dzx_in;
   } else {
     sum_dz = direct ? *dbeta_out : at::zeros({K}, fopt);
     sum_dzx = direct ? *dgamma_out : at::zeros({K}, fopt);
-    launch_bnact_bwd_reduce(dy.data_ptr(), y.data_ptr(), convout.data_ptr(),
-                            save_mean.data_ptr<float>(),
-                            save_invstd.data_ptr<float>(),
-                            gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                            sum_dz.data_ptr<float>(),
-                            sum_dzx.data_ptr<float>(),
-                            (long)p.M, K, mask_mode, st);
+    if (!own)
+      launch_bnact_bwd_reduce(dy.data_ptr(), y.data_ptr(),
+                              convout.data_ptr(),
+                              save_mean.data_ptr<float>(),
+                              save_invstd.data_ptr<float>(),
+                              gamma.data_ptr<float>(),
+                              beta.data_ptr<float>(),
+                              sum_dz.data_ptr<float>(),
+                              sum_dzx.data_ptr<float>(),
+                              (long)p.M, K, mask_mode, st);
   }
 
   Tensor dconv = empty_cl_bf16(p.Nb, K, p.Ho, p.Wo, x);
@@ -522,13 +569,22 @@ std::vector<Tensor> conv_bn_act_bwd(
     dres = empty_cl_bf16(p.Nb, K, p.Ho, p.Wo, x);
     dres_ptr = dres.data_ptr();
   }
-  launch_bn_bwd_apply(dy.data_ptr(), y.data_ptr(), convout.data_ptr(),
-                      save_mean.data_ptr<float>(),
-                      save_invstd.data_ptr<float>(), gamma.data_ptr<float>(),
-                      beta.data_ptr<float>(),
-                      sum_dz.data_ptr<float>(), sum_dzx.data_ptr<float>(),
-                      dconv.data_ptr(), dres_ptr, (long)p.M, K, mask_mode,
-                      st);
+  if (own)  // channel sums + apply in one launch (read-add-write sums)
+    launch_bn_bwd_owner(dy.data_ptr(), y.data_ptr(), convout.data_ptr(),
+                        save_mean.data_ptr<float>(),
+                        save_invstd.data_ptr<float>(),
+                        gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                        sum_dz.data_ptr<float>(), sum_dzx.data_ptr<float>(),
+                        dconv.data_ptr(), dres_ptr, (long)p.M, K, mask_mode,
+                        own, st);
+  else
+    launch_bn_bwd_apply(dy.data_ptr(), y.data_ptr(), convout.data_ptr(),
+                        save_mean.data_ptr<float>(),
+                        save_invstd.data_ptr<float>(),
+                        gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                        sum_dz.data_ptr<float>(), sum_dzx.data_ptr<float>(),
+                        dconv.data_ptr(), dres_ptr, (long)p.M, K, mask_mode,
+                        st);
 
   Tensor dw = direct ? *dw_out
                      : at::zeros({(int64_t)K, R, S, (int64_t)p.C}, fopt);
@@ -931,6 +987,77 @@ void bn_reduce_bench(Tensor dy, Tensor y, Tensor x, Tensor mean,
                           (int)C, (int)mask, cur_stream());
 }
 
+// Tuning entries for the channel-owner BN kernels: run one forward
+// (split-K slabs) or backward BN pair either as the two-kernel path
+// (lpr = 0) or as the owner kernel pinned to `lpr` lanes per row.  Return
+// the lanes-per-row actually launched (narrowed to fit C and LDS).
+int64_t bn_fwd_pair_bench(Tensor ws, c10::optional<Tensor> res, Tensor y,
+                          Tensor convout, Tensor stats, Tensor gamma,
+                          Tensor beta, Tensor rmean, Tensor rvar,
+                          Tensor smean, Tensor sinvstd, int64_t M, int64_t C,
+                          int64_t nsplit, int64_t act, int64_t lpr) {
+  TORCH_CHECK(ws.numel() >= nsplit * M * C && y.numel() >= M * C &&
+                  convout.numel() >= M * C && stats.numel() >= 2 * C,
+              "bn_fwd_pair_bench: buffers smaller than nsplit*M*C");
+  const void* rp = res.has_value() ? res->data_ptr() : nullptr;
+  auto st = cur_stream();
+  if (lpr == 0) {
+    launch_stats_reduce(ws.data_ptr<float>(), stats.data_ptr<float>(), M,
+                        (int)C, (int)nsplit, st);
+    launch_bn_apply_f32(ws.data_ptr<float>(), rp, y.data_ptr(),
+                        convout.data_ptr(), stats.data_ptr<float>(),
+                        gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                        rmean.data_ptr<float>(), rvar.data_ptr<float>(),
+                        smean.data_ptr<float>(), sinvstd.data_ptr<float>(),
+                        M, (int)C, 0.1f, 1e-5f, 1, (int)act, (int)nsplit,
+                        st);
+    return 0;
+  }
+  int own = bn_owner_fwd_pick(M, (int)C, (int)lpr);
+  TORCH_CHECK(own > 0, "owner forward kernel does not take M=", M, " C=", C);
+  launch_bn_fwd_owner(ws.data_ptr<float>(), rp, y.data_ptr(),
+                      convout.data_ptr(), gamma.data_ptr<float>(),
+                      beta.data_ptr<float>(), rmean.data_ptr<float>(),
+                      rvar.data_ptr<float>(), smean.data_ptr<float>(),
+                      sinvstd.data_ptr<float>(), M, (int)C, 0.1f, 1e-5f,
+                      (int)act, (int)nsplit, own, st);
+  return own;
+}
+
+int64_t bn_bwd_pair_bench(Tensor dy, Tensor y, Tensor x, Tensor mean,
+                          Tensor invstd, Tensor gamma, Tensor beta,
+                          Tensor sdz, Tensor sdzx, Tensor dconv,
+                          c10::optional<Tensor> dres, int64_t M, int64_t C,
+                          int64_t mask, int64_t lpr) {
+  TORCH_CHECK(dy.numel() >= M * C && y.numel() >= M * C &&
+                  x.numel() >= M * C && dconv.numel() >= M * C &&
+                  sdz.numel() >= C && sdzx.numel() >= C,
+              "bn_bwd_pair_bench: buffers smaller than M*C");
+  void* drp = dres.has_value() ? dres->data_ptr() : nullptr;
+  auto st = cur_stream();
+  if (lpr == 0) {
+    launch_bnact_bwd_reduce(dy.data_ptr(), y.data_ptr(), x.data_ptr(),
+                            mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                            gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                            sdz.data_ptr<float>(), sdzx.data_ptr<float>(), M,
+                            (int)C, (int)mask, st);
+    launch_bn_bwd_apply(dy.data_ptr(), y.data_ptr(), x.data_ptr(),
+                        mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                        gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                        sdz.data_ptr<float>(), sdzx.data_ptr<float>(),
+                        dconv.data_ptr(), drp, M, (int)C, (int)mask, st);
+    return 0;
+  }
+  int own = bn_owner_bwd_pick(M, (int)C, (int)lpr);
+  TORCH_CHECK(own > 0, "owner backward kernel does not take M=", M, " C=", C);
+  launch_bn_bwd_owner(dy.data_ptr(), y.data_ptr(), x.data_ptr(),
+                      mean.data_ptr<float>(), invstd.data_ptr<float>(),
+                      gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                      sdz.data_ptr<float>(), sdzx.data_ptr<float>(),
+                      dconv.data_ptr(), drp, M, (int)C, (int)mask, own, st);
+  return own;
+}
+
 Tensor normalize_u8(Tensor x, double mean, double std) {
   TORCH_CHECK(x.dim() == 4 && x.dtype() == torch::kUInt8 && x.is_cuda()
                   && x.is_contiguous(),
@@ -965,6 +1092,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("grad_divergence", &grad_divergence);
   m.def("normalize_u8", &normalize_u8);
   m.def("bn_reduce_bench", &bn_reduce_bench);
+  m.def("bn_fwd_pair_bench", &bn_fwd_pair_bench);
+  m.def("bn_bwd_pair_bench", &bn_bwd_pair_bench);
+  m.def("set_bn_owner", &set_bn_owner);
+  m.def("bn_owner_enabled", &bn_owner_enabled);
+  m.def("bn_owner_launches", &bn_owner_launches);
   m.def("set_deterministic", &set_deterministic);
   m.def("deterministic_enabled", &deterministic_enabled);
   m.def("set_wgrad_defer", &set_wgrad_defer);

@@ -801,6 +801,331 @@ __global__ __launch_bounds__(256) void k_bn_bwd_apply(
   }
 }
 
+// ------------------------------------- channel-owner BatchNorm (small M) ----
+// BN statistics are per channel, so a workgroup that owns a slice of
+// channels over ALL M rows can reduce and apply in one launch with only a
+// __syncthreads() between the phases — no atomics, no stats arena, and
+// the dependent reduce->apply launch boundary (1.7-1.9 us, more than the
+// streaming itself at these sizes) disappears.  Geometry: each lane owns 4
+// consecutive channels (one dwordx4 of f32 / one dwordx2 of bf16), `lpr`
+// lanes sit side by side on a row (cw = 4*lpr channels per workgroup,
+// lpr in {1,2,4,8}), and the 256/lpr row-lanes stride the M rows.  Grid =
+// C / cw workgroups, so this only pays while one workgroup can cover M
+// rows quickly (dispatch thresholds in the launchers below).
+union F4 {
+  float4 q;
+  float f[4];
+};
+
+union B4 {
+  uint2 u;
+  bf16 e[4];
+};
+
+// Sum the per-lane partials over the workgroup's row-lanes in a fixed
+// order: xor shuffles across the lanes of a wave that share a channel-lane
+// (offsets >= lpr keep tid % lpr), then the 4 wave totals through LDS.
+// Every thread returns the totals of its own 4 channels.
+DEV void owner_reduce(F4& a1, F4& a2, int lpr, int cl,
+                      float (*red)[4][32]) {
+  for (int off = 32; off >= lpr; off >>= 1) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      a1.f[e] += __shfl_xor(a1.f[e], off, 64);
+      a2.f[e] += __shfl_xor(a2.f[e], off, 64);
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane < lpr) {
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      red[0][wave][cl * 4 + e] = a1.f[e];
+      red[1][wave][cl * 4 + e] = a2.f[e];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    const int k = cl * 4 + e;
+    a1.f[e] = red[0][0][k] + red[0][1][k] + red[0][2][k] + red[0][3][k];
+    a2.f[e] = red[1][0][k] + red[1][1][k] + red[1][2][k] + red[1][3][k];
+  }
+}
+
+// Eight slab loads of one row issued back to back (slabs z0, z0+zstep, ...;
+// indices past nsplit re-read slab z0 and are dropped by slab_add8, so no
+// load sits behind a branch), then added in slab order.  One dependent
+// load per loop trip left these kernels latency-bound at ~20 GB/s per CU.
+DEV void slab_load8(const float* p, long slab, int z0, int zstep,
+                    int nsplit, float4* w) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const int z = z0 + j * zstep;
+    w[j] = *(const float4*)(p + (long)(z < nsplit ? z : z0) * slab);
+  }
+}
+
+DEV void slab_add8(F4& v, const float4* w, int z0, int zstep, int nsplit) {
+#pragma unroll
+  for (int j = 0; j < 8; j++) {
+    const bool ok = z0 + j * zstep < nsplit;
+    v.f[0] += ok ? w[j].x : 0.f;
+    v.f[1] += ok ? w[j].y : 0.f;
+    v.f[2] += ok ? w[j].z : 0.f;
+    v.f[3] += ok ? w[j].w : 0.f;
+  }
+}
+
+// Forward, split-K source (replaces k_stats_reduce + k_bn_apply_v8<true>):
+// phase 1 sums the nsplit f32 slabs per element into an LDS image
+// xs[M][cw] and accumulates (Σx, Σx²); phase 2 applies BN from that image
+// (one slab pass instead of two) and emits bf16 convout + y.  zg > 1
+// (M < row-lanes): row-lane j takes row j % M and every zg-th split
+// starting at j / M, so all lanes have loads in flight at M = 64 with
+// 32 splits; the zg partial rows are then summed in a fixed order.
+template <int ACT>
+__global__ __launch_bounds__(256) void k_bn_fwd_owner(
+    const float* __restrict__ xf, const bf16* __restrict__ res,
+    bf16* __restrict__ y, bf16* __restrict__ convout,
+    const float* __restrict__ gamma, const float* __restrict__ beta,
+    float* __restrict__ running_mean, float* __restrict__ running_var,
+    float* __restrict__ save_mean, float* __restrict__ save_invstd, int M,
+    int C, float momentum, float eps, int nsplit, int lpr, int zg) {
+  extern __shared__ float xs[];    // [max(M, M*zg)][cw]
+  __shared__ float red[2][4][32];  // [Σx|Σx²][wave][owned channel]
+  const int tid = threadIdx.x;
+  const int cw = lpr * 4;
+  const int cl = tid & (lpr - 1);
+  const int r = tid / lpr;
+  const int rl = 256 / lpr;
+  const int c0 = blockIdx.x * cw + cl * 4;
+  const long slab = (long)M * C;
+  F4 a1, a2;
+  a1.q = make_float4(0.f, 0.f, 0.f, 0.f);
+  a2.q = a1.q;
+  if (zg == 1) {
+    // two rows x 8 slabs = 16 dwordx4 loads in flight per lane; the second
+    // row of a ragged tail re-reads the first and is dropped
+    for (int m0 = r; m0 < M; m0 += 2 * rl) {
+      const int m1 = m0 + rl;
+      const bool ok1 = m1 < M;
+      const float* p0 = xf + (long)m0 * C + c0;
+      const float* p1 = xf + (long)(ok1 ? m1 : m0) * C + c0;
+      F4 v0, v1;
+      v0.q = make_float4(0.f, 0.f, 0.f, 0.f);
+      v1.q = v0.q;
+      for (int z0 = 0; z0 < nsplit; z0 += 8) {
+        float4 w0[8], w1[8];
+        slab_load8(p0, slab, z0, 1, nsplit, w0);
+        slab_load8(p1, slab, z0, 1, nsplit, w1);
+        slab_add8(v0, w0, z0, 1, nsplit);
+        slab_add8(v1, w1, z0, 1, nsplit);
+      }
+      *(float4*)(xs + m0 * cw + cl * 4) = v0.q;
+      if (ok1) *(float4*)(xs + m1 * cw + cl * 4) = v1.q;
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        const float u = ok1 ? v1.f[e] : 0.f;
+        a1.f[e] += v0.f[e];
+        a2.f[e] += v0.f[e] * v0.f[e];
+        a1.f[e] += u;
+        a2.f[e] += u * u;
+      }
+    }
+  } else {
+    if (r < M * zg) {
+      const int m = r % M, g = r / M;
+      const float* p = xf + (long)m * C + c0;
+      F4 v;
+      v.q = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int z0 = g; z0 < nsplit; z0 += 8 * zg) {
+        float4 w[8];
+        slab_load8(p, slab, z0, zg, nsplit, w);
+        slab_add8(v, w, z0, zg, nsplit);
+      }
+      *(float4*)(xs + r * cw + cl * 4) = v.q;
+    }
+    __syncthreads();
+    if (r < M) {
+      F4 v;
+      v.q = *(const float4*)(xs + r * cw + cl * 4);
+      for (int g = 1; g < zg; g++) {
+        float4 w = *(const float4*)(xs + (g * M + r) * cw + cl * 4);
+        v.f[0] += w.x; v.f[1] += w.y; v.f[2] += w.z; v.f[3] += w.w;
+      }
+      // slot r is read by this thread only (others read g*M + their row)
+      *(float4*)(xs + r * cw + cl * 4) = v.q;
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        a1.f[e] = v.f[e];
+        a2.f[e] = v.f[e] * v.f[e];
+      }
+    }
+  }
+  owner_reduce(a1, a2, lpr, cl, red);
+  const float invM = 1.f / (float)M;
+  float ga[4], be[4];
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    const int c = c0 + e;
+    float mean = a1.f[e] * invM;
+    float var = fmaxf(a2.f[e] * invM - mean * mean, 0.f);
+    float istd = rsqrtf(var + eps);
+    if (r == 0) {
+      save_mean[c] = mean;
+      save_invstd[c] = istd;
+      // unbiased running var like torch.nn.BatchNorm2d
+      float ub = (M > 1) ? var * (float)M / (float)(M - 1) : var;
+      running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mean;
+      running_var[c] = (1.f - momentum) * running_var[c] + momentum * ub;
+    }
+    ga[e] = gamma[c] * istd;
+    be[e] = beta[c] - mean * ga[e];   // y = ga*x + be  [+res] [act]
+  }
+  // every xs row is re-read by the thread that wrote it
+  for (int m = r; m < M; m += rl) {
+    const long i = (long)m * C + c0;
+    F4 v;
+    v.q = *(const float4*)(xs + m * cw + cl * 4);
+    B4 co, r4, out;
+#pragma unroll
+    for (int e = 0; e < 4; e++) co.e[e] = f2b(v.f[e]);
+    *(uint2*)(convout + i) = co.u;
+    if (res != nullptr) r4.u = *(const uint2*)(res + i);
+#pragma unroll
+    for (int e = 0; e < 4; e++) {
+      float t = fmaf(ga[e], v.f[e], be[e]);
+      if (res != nullptr) t += b2f(r4.e[e]);
+      if (ACT == 1) t = fmaxf(t, 0.f);
+      else if (ACT == 2) t = fminf(fmaxf(t, 0.f), 6.f);  // ReLU6
+      out.e[e] = f2b(t);
+    }
+    *(uint2*)(y + i) = out.u;
+  }
+}
+
+// dz = dy gated by the activation mask (mask algebra of the reduce
+// kernels: 1/3 read the mask from y, 2/4 recover it from convout).
+template <int MASK>
+DEV float owner_dz(float g, float xe, float yv, float ga, float gb) {
+  if (MASK == 1) {
+    if (yv <= 0.f) g = 0.f;
+  } else if (MASK == 2) {
+    if (fmaf(ga, xe, gb) <= 0.f) g = 0.f;
+  } else if (MASK == 3) {
+    if (yv <= 0.f || yv >= 6.f) g = 0.f;
+  } else if (MASK == 4) {
+    float bn = fmaf(ga, xe, gb);
+    if (bn <= 0.f || bn >= 6.f) g = 0.f;
+  }
+  return g;
+}
+
+// Rows m0, m0+rl, m0+2rl, m0+3rl of dy / convout (/ y for the masks that
+// read it) issued back to back: up to 12 loads in flight per lane.  Rows
+// past M re-read row m0, so no load sits behind a branch; the callers drop
+// them.  y4 is zero where the mask does not read y.
+template <int MASK>
+DEV void owner_load4(const bf16* __restrict__ dy, const bf16* __restrict__ x,
+                     const bf16* __restrict__ yout, int m0, int rl, int M,
+                     int C, int c0, B4* d4, B4* x4, B4* y4) {
+#pragma unroll
+  for (int u = 0; u < 4; u++) {
+    const int m = m0 + u * rl;
+    const long i = (long)(m < M ? m : m0) * C + c0;
+    d4[u].u = *(const uint2*)(dy + i);
+    x4[u].u = *(const uint2*)(x + i);
+    if (MASK == 1 || MASK == 3) y4[u].u = *(const uint2*)(yout + i);
+    else y4[u].u = make_uint2(0u, 0u);
+  }
+}
+
+// Backward, bf16 dy (replaces k_bnact_bwd_reduce + k_bn_bwd_apply_v8):
+// phase 1 accumulates Σdz and Σ(dz·xhat) with the reduce kernels' mask
+// algebra; phase 2 re-reads the same rows (a workgroup's share is a few
+// tens of KB, L1/L2-hot) and writes dconv = A·dz − D·x + E and dres = dz.
+// sum_dz/sum_dzx double as dbeta/dgamma and may be flat .grad views that
+// accumulate across backwards: the single owner does a plain
+// read-add-write, and the apply uses THIS call's sums.
+template <int MASK>
+__global__ __launch_bounds__(256) void k_bn_bwd_owner(
+    const bf16* __restrict__ dy, const bf16* __restrict__ yout,
+    const bf16* __restrict__ x, const float* __restrict__ save_mean,
+    const float* __restrict__ save_invstd, const float* __restrict__ gamma,
+    const float* __restrict__ beta, float* __restrict__ sum_dz,
+    float* __restrict__ sum_dzx, bf16* __restrict__ dconv,
+    bf16* __restrict__ dres, int M, int C, int lpr) {
+  __shared__ float red[2][4][32];  // [Σdz|Σdzx][wave][owned channel]
+  const int tid = threadIdx.x;
+  const int cw = lpr * 4;
+  const int cl = tid & (lpr - 1);
+  const int r = tid / lpr;
+  const int rl = 256 / lpr;
+  const int c0 = blockIdx.x * cw + cl * 4;
+  float mean[4], invstd[4], ga[4], gb[4];
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    mean[e] = save_mean[c0 + e];
+    invstd[e] = save_invstd[c0 + e];
+    ga[e] = gamma[c0 + e] * invstd[e];
+    gb[e] = beta[c0 + e] - mean[e] * ga[e];
+  }
+  F4 adz, adzx;
+  adz.q = make_float4(0.f, 0.f, 0.f, 0.f);
+  adzx.q = adz.q;
+  for (int m0 = r; m0 < M; m0 += 4 * rl) {
+    B4 d4[4], x4[4], y4[4];
+    owner_load4<MASK>(dy, x, yout, m0, rl, M, C, c0, d4, x4, y4);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const bool ok = m0 + u * rl < M;
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        float xe = b2f(x4[u].e[e]);
+        float g = owner_dz<MASK>(b2f(d4[u].e[e]), xe, b2f(y4[u].e[e]),
+                                 ga[e], gb[e]);
+        g = ok ? g : 0.f;
+        adz.f[e] += g;
+        adzx.f[e] += g * (xe - mean[e]) * invstd[e];
+      }
+    }
+  }
+  owner_reduce(adz, adzx, lpr, cl, red);
+  const float invM = 1.f / (float)M;
+  float D[4], E[4];
+#pragma unroll
+  for (int e = 0; e < 4; e++) {
+    if (r == 0) {
+      sum_dz[c0 + e] += adz.f[e];
+      sum_dzx[c0 + e] += adzx.f[e];
+    }
+    D[e] = ga[e] * invstd[e] * adzx.f[e] * invM;
+    E[e] = D[e] * mean[e] - ga[e] * adz.f[e] * invM;
+  }
+  for (int m0 = r; m0 < M; m0 += 4 * rl) {
+    B4 d4[4], x4[4], y4[4];
+    owner_load4<MASK>(dy, x, yout, m0, rl, M, C, c0, d4, x4, y4);
+#pragma unroll
+    for (int u = 0; u < 4; u++) {
+      const int m = m0 + u * rl;
+      if (m >= M) break;
+      const long i = (long)m * C + c0;
+      B4 dc4, dr4;
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        float xv = b2f(x4[u].e[e]);
+        float g = owner_dz<MASK>(b2f(d4[u].e[e]), xv, b2f(y4[u].e[e]),
+                                 ga[e], gb[e]);
+        dr4.e[e] = f2b(g);
+        float t = fmaf(ga[e], g, E[e]);
+        dc4.e[e] = f2b(fmaf(-D[e], xv, t));
+      }
+      if (dres != nullptr) *(uint2*)(dres + i) = dr4.u;
+      *(uint2*)(dconv + i) = dc4.u;
+    }
+  }
+}
+
 // ------------------------------------------------------- depthwise conv ----
 // MobileNet-family depthwise 3x3 (generic R,S ≤ 5): channel c maps to
 // itself, so the kernel is a per-channel stencil — bandwidth-bound, no
@@ -1896,6 +2221,119 @@ void launch_bn_bwd_apply(const void* dy, const void* yout, const void* x,
     default: LA(0); break;
   }
 #undef LA
+}
+
+// ---- channel-owner BN dispatch ---------------------------------------------
+// Runtime switch (set_bn_owner) + env knobs.  The owner kernels run on
+// C/(4*lpr) workgroups, so they only pay while one workgroup covers all M
+// rows quickly: M limits per direction (HZ_BN_OWNER_FWD_MMAX /
+// HZ_BN_OWNER_BWD_MMAX) and lanes-per-row (HZ_BN_OWNER_FWD_LPR /
+// HZ_BN_OWNER_BWD_LPR; wider = full cache lines per row, narrower = more
+// workgroups) come from scripts/gpu_bn_owner_sweep.py — docs/TUNING.md.
+static int g_bn_owner = [] {
+  const char* e = getenv("HZ_BN_OWNER");
+  return e ? atoi(e) : 1;
+}();
+static long g_owner_fwd_launches = 0, g_owner_bwd_launches = 0;
+
+void set_kernels_bn_owner(int on) { g_bn_owner = on; }
+int kernels_bn_owner() { return g_bn_owner; }
+void bn_owner_launch_counts(long* fwd, long* bwd) {
+  *fwd = g_owner_fwd_launches;
+  *bwd = g_owner_bwd_launches;
+}
+
+static long env_long(const char* name, long dflt) {
+  const char* e = getenv(name);
+  return e ? atol(e) : dflt;
+}
+
+// LDS image budget of the forward kernel (static LDS + this stays inside
+// the 64 KB a kernel gets without opting in to more).
+constexpr long kOwnerFwdLdsBytes = 60 * 1024;
+
+// widest lanes-per-row <= want (power of two, <= 8) whose channel slice
+// divides C; C % 8 == 0 guarantees lpr = 2 fits.
+static int owner_lpr(int C, int want) {
+  int lpr = 8;
+  while (lpr > 1 && (lpr > want || C % (4 * lpr) != 0)) lpr >>= 1;
+  return lpr;
+}
+
+// Returns the lanes-per-row to launch with, or 0 when the shape keeps the
+// two-kernel path.  lpr_req > 0 pins the width (sweeps); it is still
+// narrowed to fit C and the LDS image.
+int bn_owner_fwd_pick(long M, int C, int lpr_req) {
+  // swept: wins at M <= 512 (layer3/4 of the flagship), ties the pair at
+  // M = 1024 where 16 workgroups stream 4 MB of slabs; 2 lanes per row
+  // won at every winning shape
+  static long mmax = env_long("HZ_BN_OWNER_FWD_MMAX", 512);
+  static int want = (int)env_long("HZ_BN_OWNER_FWD_LPR", 2);
+  if (!g_bn_owner || g_det_kernels || (C & 7) != 0 || M < 1) return 0;
+  if (lpr_req <= 0 && M > mmax) return 0;
+  int lpr = owner_lpr(C, lpr_req > 0 ? lpr_req : want);
+  while (lpr > 1 && M * lpr * 16 > kOwnerFwdLdsBytes) lpr >>= 1;
+  if (M * lpr * 16 > kOwnerFwdLdsBytes) return 0;
+  return lpr;
+}
+
+int bn_owner_bwd_pick(long M, int C, int lpr_req) {
+  // swept: wins up to M = 1024, loses 2x at M = 4096 (C = 64 leaves 8-16
+  // workgroups reading 8 bytes of every 128-byte row).  Lanes per row
+  // (0 = auto): narrow rows at large M for more workgroups, full lines at
+  // small M where C/32 workgroups are still plenty.
+  static long mmax = env_long("HZ_BN_OWNER_BWD_MMAX", 1024);
+  static int want = (int)env_long("HZ_BN_OWNER_BWD_LPR", 0);
+  if (!g_bn_owner || g_det_kernels || (C & 7) != 0 || M < 1) return 0;
+  if (M > (lpr_req > 0 ? (long)1 << 24 : mmax)) return 0;
+  // swept: M*C = 256 Ki still wins (M=1024/C=256 8.3 vs 9.1 us, M=512/
+  // C=512 6.4 vs 7.0), M=1024/C=512 loses 2x (15.4 vs 7.7 us: the pair
+  // fills the chip there) and cost layer4 at batch 1024 0.6% of its step
+  static long emax = env_long("HZ_BN_OWNER_BWD_EMAX", 262144);
+  if (lpr_req <= 0 && M * C > emax) return 0;
+  int w = lpr_req > 0 ? lpr_req : want;
+  if (w <= 0) w = (int)max((long)2, min((long)8, 1024 / M));
+  return owner_lpr(C, w);
+}
+
+void launch_bn_fwd_owner(const float* ws, const void* res, void* y,
+                         void* convout, const float* gamma,
+                         const float* beta, float* rmean, float* rvar,
+                         float* smean, float* sinvstd, long M, int C,
+                         float momentum, float eps, int act, int nsplit,
+                         int lpr, hipStream_t st) {
+  const int rl = 256 / lpr;
+  int zg = 1;
+  if (M < rl) zg = (int)max((long)1, min((long)nsplit, rl / M));
+  const size_t lds = (size_t)M * zg * lpr * 16;
+  dim3 grid(C / (4 * lpr));
+#define LO(AC) k_bn_fwd_owner<AC><<<grid, 256, lds, st>>>( \
+    ws, (const bf16*)res, (bf16*)y, (bf16*)convout, gamma, beta, rmean, \
+    rvar, smean, sinvstd, (int)M, C, momentum, eps, nsplit, lpr, zg)
+  if (act == 1) LO(1); else if (act == 2) LO(2); else LO(0);
+#undef LO
+  g_owner_fwd_launches++;
+}
+
+void launch_bn_bwd_owner(const void* dy, const void* yout, const void* x,
+                         const float* smean, const float* sinvstd,
+                         const float* gamma, const float* beta,
+                         float* sum_dz, float* sum_dzx, void* dconv,
+                         void* dres, long M, int C, int mask_mode, int lpr,
+                         hipStream_t st) {
+  dim3 grid(C / (4 * lpr));
+#define LO(MK) k_bn_bwd_owner<MK><<<grid, 256, 0, st>>>( \
+    (const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, sinvstd, \
+    gamma, beta, sum_dz, sum_dzx, (bf16*)dconv, (bf16*)dres, (int)M, C, lpr)
+  switch (mask_mode) {
+    case 1: LO(1); break;
+    case 2: LO(2); break;
+    case 3: LO(3); break;
+    case 4: LO(4); break;
+    default: LO(0); break;
+  }
+#undef LO
+  g_owner_bwd_launches++;
 }
 
 void launch_dw_fwd(const void* x, const void* w, void* y, float* stats,
