@@ -21,14 +21,20 @@ def run_data_parallel(world_size: int, epochs: int, sample_size: int,
                       batch_size: int = 64, model_name: str = "resnet18",
                       backend=None, synthetic=None, lr: float = 1e-3,
                       optimizer_name: str = "adam", engine: str = "auto",
-                      checkpoint_path=None, per_step_barrier: bool = False):
+                      checkpoint_path=None, per_step_barrier: bool = False,
+                      augment: bool = False, augment_pad: int = 4):
     """Launcher parity with reference ``run_data_parallel``
-    (``data_parallel_train.py:233-291``). Returns the combined DataFrame."""
+    (``data_parallel_train.py:233-291``). Returns the combined DataFrame.
+
+    ``augment`` (an extension over the reference): random crop with
+    ``augment_pad`` zero padding + horizontal flip, fused into the on-device
+    normalize."""
     return run_workers(dp_worker, world_size, epochs, sample_size, logs_dir,
                        timeout_base=120,
                        extra_args=(batch_size, model_name, backend, synthetic,
                                    lr, optimizer_name, engine,
-                                   checkpoint_path, per_step_barrier))
+                                   checkpoint_path, per_step_barrier,
+                                   augment, augment_pad))
 
 
 def main():
@@ -60,6 +66,12 @@ def main():
                     help="restore the reference's full-world barrier after "
                          "every step (exact idle_time semantics; the "
                          "default barriers per epoch)")
+    ap.add_argument("--augment", action="store_true",
+                    help="RandomCrop(32, padding=augment_pad) + "
+                         "RandomHorizontalFlip, fused into the on-device "
+                         "normalize kernel (default off)")
+    ap.add_argument("--augment_pad", type=int, default=4,
+                    help="zero padding of the random crop (with --augment)")
     args = ap.parse_args()
     if args.deterministic:
         import os
@@ -68,7 +80,8 @@ def main():
                            args.logs_dir, args.batch_size, args.model,
                            args.backend, args.synthetic, args.lr,
                            args.optimizer, args.engine, args.checkpoint,
-                           args.per_step_barrier)
+                           args.per_step_barrier, args.augment,
+                           args.augment_pad)
     if df is not None:
         print(df.tail(args.world_size).to_string(index=False))
 

@@ -37,15 +37,29 @@ from ..runtime.distributed import (DistContext, barrier, setup_distributed,
 from ..utils.seed import seed_everything
 
 
-def _to_device(x, y, ctx: DistContext):
+def _to_device(x, y, ctx: DistContext, augmenter=None):
     if ctx.is_gpu:
         x = x.to(ctx.device, non_blocking=True)
         if x.dtype == torch.uint8:  # raw loader: normalize on-device
-            from ..data.cifar import normalize_uint8
-            x = normalize_uint8(x)
+            if augmenter is not None:
+                x = augmenter(x)
+            else:
+                from ..data.cifar import normalize_uint8
+                x = normalize_uint8(x)
         x = x.to(memory_format=torch.channels_last).to(torch.bfloat16)
         y = y.to(ctx.device, non_blocking=True)
+    elif augmenter is not None:  # raw uint8 on CPU -> normalized f32
+        x = augmenter(x)
     return x, y
+
+
+def _make_augmenter(rank: int, pad: int, device):
+    """Per-rank augmentation stream: ranks hold different shards, so the key
+    mixes the rank into the shared seed."""
+    from ..data.augment import DeviceAugment
+    from ..utils.seed import DEFAULT_SEED
+    return DeviceAugment((DEFAULT_SEED << 32) | rank, pad=pad, flip=True,
+                         device=device)
 
 
 def select_engine(engine: str, ctx: DistContext, model_name: str) -> str:
@@ -71,7 +85,8 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
                   probe_divergence: bool = True, log_progress: bool = True,
                   use_graph: bool = True,
                   checkpoint_path: Optional[str] = None,
-                  per_step_barrier: bool = False):
+                  per_step_barrier: bool = False,
+                  augment: bool = False, augment_pad: int = 4):
     """DP training on the flat fast path — the entrypoint-facing version of
     the bench.py flagship step (the parity entrypoint
     should run the best path we have).
@@ -91,6 +106,13 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
       bucket-overlapped) is bench.py's flagship configuration;
     * loss/accuracy/divergence accumulate in static device scalars read
       once per epoch (no per-step sync); CSV schema unchanged.
+
+    ``augment``: the normalize kernel is replaced by the fused random
+    crop + flip + normalize kernel (plus a one-thread counter bump: one
+    extra dispatch per step); its step counter
+    lives on the device and advances under graph replay, and is set to
+    ``start_epoch * len(loader)`` after the capture warm-ups so a resumed
+    run continues the stream of an uninterrupted one.
 
     Capture runs 3 warmup steps on the first batch shape; parameter /
     BN-buffer / optimizer state is snapshotted before and restored after,
@@ -121,6 +143,8 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
     comm_buf = (torch.zeros_like(mgr.grad, dtype=torch.bfloat16)
                 if use_comm else None)
     inv_world = 1.0 / world
+    augmenter = _make_augmenter(rank, augment_pad, dev) if augment else None
+    to_norm = augmenter if augmenter is not None else normalize_uint8
 
     # static buffers + on-device accumulators
     sx = torch.empty(batch_size, 3, 32, 32, dtype=torch.uint8, device=dev)
@@ -140,7 +164,7 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
         """Capturable device-side step up to (not including) the optimizer:
         returns loss; leaves complete grads in mgr.grad and, when
         ``use_comm``, the bf16 pack in comm_buf."""
-        x = normalize_uint8(x_u8) \
+        x = to_norm(x_u8) \
             .to(memory_format=torch.channels_last).to(torch.bfloat16)
         logits = model(x)
         loss = cross_entropy(logits, y)
@@ -231,6 +255,8 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
         if log_progress and rank == 0:
             print(f"[dp-flat] resumed from {checkpoint_path} "
                   f"(epoch {start_epoch})", flush=True)
+    if augmenter is not None:  # the capture warm-ups advanced the counter
+        augmenter.set_step(start_epoch * len(loader))
 
     prof = StepProfiler(dev)
     writer = MetricsWriter(logs_dir, rank, sample_size,
@@ -326,7 +352,8 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
              synthetic: Optional[bool] = None, data_dir: str = "./data",
              probe_divergence: bool = True, log_progress: bool = True,
              checkpoint_path: Optional[str] = None,
-             per_step_barrier: bool = False):
+             per_step_barrier: bool = False,
+             augment: bool = False, augment_pad: int = 4):
     """Run the DP training loop for this rank; writes the per-worker CSV.
 
     ``per_step_barrier=True`` restores the reference's full-world barrier
@@ -338,7 +365,11 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
     seed_everything(rank=rank)
     loader, sampler = get_dataloader(rank, world, batch_size, sample_size,
                                      strategy="dp", data_dir=data_dir,
-                                     synthetic=synthetic, raw=ctx.is_gpu)
+                                     synthetic=synthetic,
+                                     raw=ctx.is_gpu or augment)
+    augmenter = (_make_augmenter(rank, augment_pad,
+                                 ctx.device if ctx.is_gpu else "cpu")
+                 if augment else None)
 
     model = build_model(model_name, num_classes=10)
     if ctx.is_gpu:
@@ -365,6 +396,8 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
         if log_progress and rank == 0:
             print(f"[dp] resumed from {checkpoint_path} "
                   f"(epoch {start_epoch})", flush=True)
+    if augmenter is not None:
+        augmenter.set_step(start_epoch * len(loader))
 
     for epoch in range(start_epoch, epochs):
         if sampler is not None:
@@ -381,7 +414,7 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
             cpu_samples.append(cpu)
             mem_samples.append(mem)
 
-            x, y = _to_device(x, y, ctx)
+            x, y = _to_device(x, y, ctx, augmenter)
             with prof.compute():
                 optimizer.zero_grad(set_to_none=True)
                 logits = ddp(x)
@@ -439,7 +472,8 @@ def dp_worker(rank: int, world_size: int, epochs: int, sample_size: int,
               synthetic: Optional[bool] = None, lr: float = 1e-3,
               optimizer_name: str = "adam", engine: str = "auto",
               checkpoint_path: Optional[str] = None,
-              per_step_barrier: bool = False):
+              per_step_barrier: bool = False,
+              augment: bool = False, augment_pad: int = 4):
     """Spawned worker entry (reference ``data_parallel_train.py:192-230``).
 
     ``engine``: ``flat`` (default on GPU via ``auto``) runs the hipGraph /
@@ -459,13 +493,15 @@ def dp_worker(rank: int, world_size: int, epochs: int, sample_size: int,
                           synthetic=synthetic, lr=lr,
                           optimizer_name=optimizer_name,
                           checkpoint_path=checkpoint_path,
-                          per_step_barrier=per_step_barrier)
+                          per_step_barrier=per_step_barrier,
+                          augment=augment, augment_pad=augment_pad)
         else:
             train_dp(ctx, epochs, sample_size, logs_dir,
                      batch_size=batch_size, model_name=model_name,
                      synthetic=synthetic, lr=lr,
                      optimizer_name=optimizer_name,
                      checkpoint_path=checkpoint_path,
-                     per_step_barrier=per_step_barrier)
+                     per_step_barrier=per_step_barrier,
+                     augment=augment, augment_pad=augment_pad)
     finally:
         teardown_distributed(ctx)

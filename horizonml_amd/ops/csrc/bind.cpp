@@ -84,6 +84,9 @@ void launch_grad_divergence(const float*, float*, float*, float*, long, int,
                             hipStream_t);
 void launch_normalize_u8(const void*, void*, long, int, long, float, float,
                          hipStream_t);
+void launch_augment_normalize_u8(const void*, void*, void*, const int*, long,
+                                 int, int, int, int, int, float, float,
+                                 hipStream_t);
 void set_kernels_bn_owner(int);
 int kernels_bn_owner();
 void bn_owner_launch_counts(long*, long*);
@@ -1071,6 +1074,46 @@ Tensor normalize_u8(Tensor x, double mean, double std) {
   return y;
 }
 
+// normalize_u8 with a per-sample random crop (zero padding `pad`) and
+// horizontal flip folded in.  `state` = int64 {key, step}; the op advances
+// the step on the device (graph-replay safe).  `params` (int32 [N],
+// dy | dx<<8 | flip<<16) overrides the RNG and leaves `state` untouched.
+Tensor augment_normalize_u8(Tensor x, Tensor state, double mean, double std,
+                            int64_t pad, bool flip,
+                            c10::optional<Tensor> params) {
+  TORCH_CHECK(x.dim() == 4 && x.dtype() == torch::kUInt8 && x.is_cuda()
+                  && x.is_contiguous(),
+              "augment_normalize_u8 expects contiguous NCHW uint8 on GPU");
+  TORCH_CHECK(pad >= 0 && pad <= 127,
+              "augment_normalize_u8: pad must be in [0, 127], got ", pad);
+  TORCH_CHECK(state.is_cuda() && state.dtype() == torch::kInt64
+                  && state.is_contiguous() && state.numel() >= 2
+                  && state.device() == x.device(),
+              "augment_normalize_u8: state must be a contiguous int64 GPU "
+              "tensor with >= 2 elements (key, step)");
+  const long N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(N * C * H * W < (1L << 31),
+              "augment_normalize_u8: batch too large for 32-bit indexing");
+  const int* pp = nullptr;
+  if (params.has_value()) {
+    const Tensor& p = *params;
+    TORCH_CHECK(p.is_cuda() && p.dtype() == torch::kInt32
+                    && p.is_contiguous() && p.numel() == N
+                    && p.device() == x.device(),
+                "augment_normalize_u8: params must be a contiguous int32 GPU "
+                "tensor with N = ", N, " elements");
+    pp = p.data_ptr<int>();
+  }
+  auto y = at::empty({N, C, H, W},
+                     x.options().dtype(torch::kBFloat16),
+                     at::MemoryFormat::ChannelsLast);
+  launch_augment_normalize_u8(x.data_ptr(), y.data_ptr(), state.data_ptr(),
+                              pp, N, (int)C, (int)H, (int)W, (int)pad,
+                              flip ? 1 : 0, (float)mean, (float)std,
+                              cur_stream());
+  return y;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1091,6 +1134,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("permute_krsc_rsck", &permute_krsc_rsck);
   m.def("grad_divergence", &grad_divergence);
   m.def("normalize_u8", &normalize_u8);
+  m.def("augment_normalize_u8", &augment_normalize_u8, py::arg("x"),
+        py::arg("state"), py::arg("mean"), py::arg("std"), py::arg("pad"),
+        py::arg("flip"), py::arg("params") = py::none());
   m.def("bn_reduce_bench", &bn_reduce_bench);
   m.def("bn_fwd_pair_bench", &bn_fwd_pair_bench);
   m.def("bn_bwd_pair_bench", &bn_bwd_pair_bench);

@@ -1867,6 +1867,103 @@ __global__ __launch_bounds__(256) void k_normalize_u8(
   }
 }
 
+// ------------------------- fused u8 random crop + flip + batch normalize ----
+// k_normalize_u8 with RandomCrop(padding=pad) + RandomHorizontalFlip folded
+// into the gather address: output pixel (n, ho, wo) reads
+//   x[n, c, ho + dy - pad, (flip ? W-1-wo : wo) + dx - pad]
+// or the raw byte 0 where that leaves the image (padding happens BEFORE
+// the normalize, like torchvision's crop on the uint8 image), then applies
+// k_normalize_u8's exact expression, so the two kernels agree bitwise.
+// One thread per output pixel looping over c: each plane read is contiguous
+// along wo across the wave (flipped or not) and a lane writes its C adjacent
+// bf16.  Pixel indices are 32-bit (the binding checks N*C*H*W < 2^31).
+//
+// Per-sample (dy, dx, flip), RNG = true: a counter-based hash of
+// (key, step, n) with key = state[0], step = state[1] — u32 multiply / xor /
+// shift / add only; data/augment.py's augment_params is the exact mirror.
+// The op leaves state[1] = step + 1 behind so a replayed hipGraph walks the
+// stream with no host help.  Two launches: this kernel only READS state, and
+// the one-thread k_augment_step_inc behind it on the stream bumps the
+// counter — every thread sees the same step by construction.  The
+// single-launch last-block-done form (one returning atomic ticket per block
+// on one word, last ticket writes step + 1) was built and measured first:
+// the device-scope tickets serialise at ~37 ns each — +3.6 us at 256 blocks,
+// +145 us at 4096 — against ~1.8 us for the extra dispatch.
+// RNG = false: params[n] = dy | dx << 8 | flip << 16 (replay of a recorded
+// augmentation); state is not touched.  Offsets outside [0, 2*pad] are
+// memory-safe: the window test sends them to the padding value.
+DEV unsigned aug_fmix32(unsigned h) {  // murmur3 finaliser
+  h ^= h >> 16;
+  h *= 0x85ebca6bu;
+  h ^= h >> 13;
+  h *= 0xc2b2ae35u;
+  h ^= h >> 16;
+  return h;
+}
+
+template <bool RNG>
+__global__ __launch_bounds__(256) void k_augment_normalize_u8(
+    const unsigned char* __restrict__ x, bf16* __restrict__ y,
+    const unsigned long long* __restrict__ state,
+    const int* __restrict__ params, unsigned npix, int C, int H, int W,
+    int pad, int do_flip, float mean, float std) {
+  unsigned seed = 0;
+  if (RNG) {
+    const unsigned long long key = state[0], step = state[1];
+    seed = aug_fmix32(aug_fmix32(aug_fmix32((unsigned)key) ^
+                                 (unsigned)(key >> 32)) ^ (unsigned)step);
+  }
+  const unsigned HW = (unsigned)H * (unsigned)W;
+  const unsigned range = 2u * (unsigned)pad + 1u;
+  const float vpad = (0.0f / 255.0f - mean) / std;  // a raw 0 byte
+  for (unsigned p = blockIdx.x * blockDim.x + threadIdx.x; p < npix;
+       p += gridDim.x * blockDim.x) {
+    const unsigned n = p / HW, hw = p - n * HW;
+    const int ho = (int)(hw / (unsigned)W), wo = (int)(hw - ho * W);
+    int dy, dx, fl;
+    if (RNG) {
+      const unsigned t = aug_fmix32(seed ^ (n * 0x9e3779b1u));
+      dy = (int)__umulhi(aug_fmix32(t + 0x85ebca77u), range);
+      dx = (int)__umulhi(aug_fmix32(t + 2u * 0x85ebca77u), range);
+      fl = do_flip ? (int)(aug_fmix32(t + 3u * 0x85ebca77u) >> 31) : 0;
+    } else {
+      const int q = params[n];
+      dy = q & 0xff;
+      dx = (q >> 8) & 0xff;
+      fl = (q >> 16) & 1;
+    }
+    const int hi = ho + dy - pad;
+    const int wi = (fl ? W - 1 - wo : wo) + dx - pad;
+    const bool in = (unsigned)hi < (unsigned)H && (unsigned)wi < (unsigned)W;
+    const unsigned char* src =
+        x + (size_t)n * C * HW + (in ? (unsigned)(hi * W + wi) : 0u);
+    bf16* dst = y + (size_t)p * C;
+    // 4 plane loads in flight per lane (one dependent load per trip left
+    // the C = 3 case three load latencies deep).  Padding pixels and
+    // channels past C re-read a valid byte and drop it, so no load sits
+    // behind a branch.
+    for (int c0 = 0; c0 < C; c0 += 4) {
+      unsigned char b[4];
+#pragma unroll
+      for (int e = 0; e < 4; e++)
+        b[e] = src[(size_t)min(c0 + e, C - 1) * HW];
+#pragma unroll
+      for (int e = 0; e < 4; e++) {
+        // k_normalize_u8's expression (div, sub, div).  The padding select
+        // sits on the RESULT: selecting the byte let the compiler sink the
+        // select between the multiply and the subtract, which blocked the
+        // fma contraction k_normalize_u8 gets and broke bitwise agreement.
+        const float v = ((float)b[e] / 255.0f - mean) / std;
+        if (c0 + e < C) dst[c0 + e] = (bf16)(in ? v : vpad);
+      }
+    }
+  }
+}
+
+__global__ void k_augment_step_inc(unsigned long long* state) {
+  state[1] += 1;
+}
+
 __global__ void k_gdiv_finalize(float* __restrict__ sumsq,
                                 float* __restrict__ out, int skip_first) {
   if (!skip_first) out[0] += sqrtf(sumsq[0]);
@@ -2502,6 +2599,26 @@ void launch_normalize_u8(const void* x, void* y, long total, int C, long HW,
   k_normalize_u8<<<gsz(total), 256, 0, st>>>((const unsigned char*)x,
                                              (bf16*)y, total, C, HW, mean,
                                              std);
+}
+
+// params == nullptr: RNG mode (state = {key, step}; a second one-thread
+// launch advances the step on the device); otherwise explicit per-sample
+// parameters, state unused.
+void launch_augment_normalize_u8(const void* x, void* y, void* state,
+                                 const int* params, long N, int C, int H,
+                                 int W, int pad, int flip, float mean,
+                                 float std, hipStream_t st) {
+  const long npix = N * H * W;
+  const int grid = gsz(npix);
+  if (params == nullptr) {
+    k_augment_normalize_u8<true><<<grid, 256, 0, st>>>(
+        (const unsigned char*)x, (bf16*)y, (const unsigned long long*)state,
+        nullptr, (unsigned)npix, C, H, W, pad, flip, mean, std);
+    k_augment_step_inc<<<1, 1, 0, st>>>((unsigned long long*)state);
+  } else
+    k_augment_normalize_u8<false><<<grid, 256, 0, st>>>(
+        (const unsigned char*)x, (bf16*)y, nullptr, params, (unsigned)npix,
+        C, H, W, pad, flip, mean, std);
 }
 
 }  // extern "C"
