@@ -22,19 +22,31 @@ def run_data_parallel(world_size: int, epochs: int, sample_size: int,
                       backend=None, synthetic=None, lr: float = 1e-3,
                       optimizer_name: str = "adam", engine: str = "auto",
                       checkpoint_path=None, per_step_barrier: bool = False,
-                      augment: bool = False, augment_pad: int = 4):
+                      augment: bool = False, augment_pad: int = 4,
+                      lr_schedule: str = "constant",
+                      warmup_epochs: float = 0.0, min_lr: float = 0.0,
+                      lr_milestones=(), lr_gamma: float = 0.1,
+                      weight_decay: float = 0.0, nesterov: bool = False,
+                      decoupled_wd: bool = False,
+                      label_smoothing: float = 0.0):
     """Launcher parity with reference ``run_data_parallel``
     (``data_parallel_train.py:233-291``). Returns the combined DataFrame.
 
     ``augment`` (an extension over the reference): random crop with
     ``augment_pad`` zero padding + horizontal flip, fused into the on-device
-    normalize."""
+    normalize.  ``lr_schedule`` … ``label_smoothing`` (extensions too): the
+    training-recipe knobs of ``engine.dp.train_dp_flat``; epoch quantities
+    are converted to steps with the rank's loader length."""
     return run_workers(dp_worker, world_size, epochs, sample_size, logs_dir,
                        timeout_base=120,
                        extra_args=(batch_size, model_name, backend, synthetic,
                                    lr, optimizer_name, engine,
                                    checkpoint_path, per_step_barrier,
-                                   augment, augment_pad))
+                                   augment, augment_pad, lr_schedule,
+                                   warmup_epochs, min_lr,
+                                   tuple(lr_milestones), lr_gamma,
+                                   weight_decay, nesterov, decoupled_wd,
+                                   label_smoothing))
 
 
 def main():
@@ -72,6 +84,28 @@ def main():
                          "normalize kernel (default off)")
     ap.add_argument("--augment_pad", type=int, default=4,
                     help="zero padding of the random crop (with --augment)")
+    ap.add_argument("--lr_schedule", type=str, default="constant",
+                    choices=["constant", "cosine", "linear", "multistep"],
+                    help="learning-rate schedule over the whole run; the "
+                         "flat engine reads it on the device, inside the "
+                         "captured step (default constant = --lr)")
+    ap.add_argument("--warmup_epochs", type=float, default=0.0,
+                    help="linear warm-up to --lr over this many epochs")
+    ap.add_argument("--min_lr", type=float, default=0.0,
+                    help="final lr of the cosine / linear schedules")
+    ap.add_argument("--lr_milestones", type=int, nargs="*", default=[],
+                    help="epochs at which multistep multiplies the lr by "
+                         "--lr_gamma")
+    ap.add_argument("--lr_gamma", type=float, default=0.1)
+    ap.add_argument("--weight_decay", type=float, default=0.0,
+                    help="L2 weight decay on every parameter (BN and bias "
+                         "included)")
+    ap.add_argument("--nesterov", action="store_true",
+                    help="Nesterov momentum (with --optimizer sgd)")
+    ap.add_argument("--decoupled_wd", action="store_true",
+                    help="AdamW: decoupled weight decay (with --optimizer "
+                         "adam)")
+    ap.add_argument("--label_smoothing", type=float, default=0.0)
     args = ap.parse_args()
     if args.deterministic:
         import os
@@ -81,7 +115,11 @@ def main():
                            args.backend, args.synthetic, args.lr,
                            args.optimizer, args.engine, args.checkpoint,
                            args.per_step_barrier, args.augment,
-                           args.augment_pad)
+                           args.augment_pad, args.lr_schedule,
+                           args.warmup_epochs, args.min_lr,
+                           args.lr_milestones, args.lr_gamma,
+                           args.weight_decay, args.nesterov,
+                           args.decoupled_wd, args.label_smoothing)
     if df is not None:
         print(df.tail(args.world_size).to_string(index=False))
 

@@ -122,19 +122,36 @@ def build_engine_optimizer(module, params, name: str, lr: float, device):
 
 
 def build_optimizer(params, name: str = "adam", lr: float = 1e-3,
-                    momentum: float = 0.9, weight_decay: float = 0.0):
+                    momentum: float = 0.9, weight_decay: float = 0.0,
+                    nesterov: bool = False, decoupled_wd: bool = False):
     """Reference default: Adam(lr=1e-3) (``data_parallel_train.py:205``).
-    The north star also names the SGD step — both supported."""
+    The north star also names the SGD step — both supported.
+    ``decoupled_wd`` selects ``torch.optim.AdamW``."""
     name = name.lower()
     # foreach=True batches the per-parameter update into multi-tensor
     # kernels — the eager engine paths are launch-bound otherwise
     if name == "adam":
-        return torch.optim.Adam(params, lr=lr, weight_decay=weight_decay,
-                                foreach=True)
+        cls = torch.optim.AdamW if decoupled_wd else torch.optim.Adam
+        return cls(params, lr=lr, weight_decay=weight_decay, foreach=True)
     if name == "sgd":
         return torch.optim.SGD(params, lr=lr, momentum=momentum,
-                               weight_decay=weight_decay, foreach=True)
+                               weight_decay=weight_decay, nesterov=nesterov,
+                               foreach=True)
     raise ValueError(f"unknown optimizer {name!r}")
+
+
+def build_schedule(kind: str, lr: float, epochs: int, steps_per_epoch: int,
+                   warmup_epochs: float = 0.0, min_lr: float = 0.0,
+                   milestones=(), gamma: float = 0.1):
+    """The ``--lr_schedule`` family of flags as an ``LRSchedule``, or ``None``
+    for the default (constant, no warm-up): the engines then run exactly the
+    unscheduled step."""
+    if kind == "constant" and not warmup_epochs > 0:
+        return None
+    from .schedule import schedule_from_epochs
+    return schedule_from_epochs(kind, lr, epochs, steps_per_epoch,
+                                warmup_epochs=warmup_epochs, min_lr=min_lr,
+                                milestones=milestones or (), gamma=gamma)
 
 
 def progress_iter(loader, desc: str, enabled: bool = True):

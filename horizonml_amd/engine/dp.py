@@ -26,7 +26,7 @@ import torch.nn.functional as F
 
 from ..data import get_dataloader
 from ..engine.common import (GradDivergenceProbe, Meters,
-                             build_optimizer, progress_iter)
+                             build_optimizer, build_schedule, progress_iter)
 from ..models import build_model
 from ..parallel import BucketedDataParallel
 from ..profiling.metrics import (EpochMetrics, MetricsWriter,
@@ -86,7 +86,11 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
                   use_graph: bool = True,
                   checkpoint_path: Optional[str] = None,
                   per_step_barrier: bool = False,
-                  augment: bool = False, augment_pad: int = 4):
+                  augment: bool = False, augment_pad: int = 4,
+                  lr_schedule: str = "constant", warmup_epochs: float = 0.0,
+                  min_lr: float = 0.0, lr_milestones=(), lr_gamma: float = 0.1,
+                  weight_decay: float = 0.0, nesterov: bool = False,
+                  decoupled_wd: bool = False, label_smoothing: float = 0.0):
     """DP training on the flat fast path — the entrypoint-facing version of
     the bench.py flagship step (the parity entrypoint
     should run the best path we have).
@@ -114,6 +118,16 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
     ``start_epoch * len(loader)`` after the capture warm-ups so a resumed
     run continues the stream of an uninterrupted one.
 
+    ``lr_schedule`` / ``warmup_epochs`` / ``min_lr`` / ``lr_milestones`` /
+    ``lr_gamma`` (epochs, converted with ``len(loader)``): the schedule is
+    built into the fused optimizer as a device table indexed by the device
+    step counter, so the captured step walks it with no host work; the
+    counter is reset after the capture warm-ups and positioned at
+    ``start_epoch * len(loader)`` on a resume whose checkpoint carried none.
+    ``weight_decay`` / ``nesterov`` / ``decoupled_wd`` (AdamW) reach the
+    fused kernels, ``label_smoothing`` the fused cross-entropy.  All default
+    to the unscheduled step, which launches the same kernels as before.
+
     Capture runs 3 warmup steps on the first batch shape; parameter /
     BN-buffer / optimizer state is snapshotted before and restored after,
     so training still starts from the seeded init.  Ragged final batches
@@ -134,8 +148,13 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
                                      synthetic=synthetic, raw=True)
     model = build_model(model_name, num_classes=10).to(dev)
     mgr = FlatParamManager(model, dev)
-    opt = (HorizonAdam(mgr, lr=lr) if optimizer_name == "adam"
-           else HorizonSGD(mgr, lr=lr))
+    sched = build_schedule(lr_schedule, lr, epochs, len(loader),
+                           warmup_epochs, min_lr, lr_milestones, lr_gamma)
+    opt = (HorizonAdam(mgr, lr=lr, weight_decay=weight_decay,
+                       schedule=sched, decoupled_wd=decoupled_wd)
+           if optimizer_name == "adam"
+           else HorizonSGD(mgr, lr=lr, weight_decay=weight_decay,
+                           schedule=sched, nesterov=nesterov))
     import torch.distributed as dist
     force_comm = (os.environ.get("HZ_FORCE_COMM") == "1" and world == 1
                   and dist.is_initialized() and ctx.backend == "nccl")
@@ -167,7 +186,7 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
         x = to_norm(x_u8) \
             .to(memory_format=torch.channels_last).to(torch.bfloat16)
         logits = model(x)
-        loss = cross_entropy(logits, y)
+        loss = cross_entropy(logits, y, label_smoothing)
         loss.backward()
         ext.flush_wgrad()  # batched deferred wgrads -> grads complete
         if use_comm:
@@ -235,9 +254,10 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
             mgr.grad.zero_()
             mgr.stats_arena.zero_()
             if isinstance(opt, HorizonAdam):
-                opt.m.zero_(), opt.v.zero_(), opt.step_t.zero_()
+                opt.m.zero_(), opt.v.zero_()
             elif opt.mom is not None:
                 opt.mom.zero_()
+            opt.set_step(0)  # Adam's step_t, scheduled SGD's too
             loss_acc.zero_(), corr_acc.zero_()
             if probe_divergence:
                 prev.zero_(), sumsq.zero_(), div_acc.zero_()
@@ -255,6 +275,10 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
         if log_progress and rank == 0:
             print(f"[dp-flat] resumed from {checkpoint_path} "
                   f"(epoch {start_epoch})", flush=True)
+        # a checkpoint from before SGD kept a step counter carries none
+        if (sched is not None
+                and state.get("optimizer", {}).get("step_t") is None):
+            opt.set_step(start_epoch * len(loader))
     if augmenter is not None:  # the capture warm-ups advanced the counter
         augmenter.set_step(start_epoch * len(loader))
 
@@ -353,7 +377,11 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
              probe_divergence: bool = True, log_progress: bool = True,
              checkpoint_path: Optional[str] = None,
              per_step_barrier: bool = False,
-             augment: bool = False, augment_pad: int = 4):
+             augment: bool = False, augment_pad: int = 4,
+             lr_schedule: str = "constant", warmup_epochs: float = 0.0,
+             min_lr: float = 0.0, lr_milestones=(), lr_gamma: float = 0.1,
+             weight_decay: float = 0.0, nesterov: bool = False,
+             decoupled_wd: bool = False, label_smoothing: float = 0.0):
     """Run the DP training loop for this rank; writes the per-worker CSV.
 
     ``per_step_barrier=True`` restores the reference's full-world barrier
@@ -375,7 +403,11 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
     if ctx.is_gpu:
         model = model.to(ctx.device)
     ddp = BucketedDataParallel(model, profiler=None)
-    optimizer = build_optimizer(model.parameters(), optimizer_name, lr=lr)
+    optimizer = build_optimizer(model.parameters(), optimizer_name, lr=lr,
+                                weight_decay=weight_decay, nesterov=nesterov,
+                                decoupled_wd=decoupled_wd)
+    sched = build_schedule(lr_schedule, lr, epochs, len(loader),
+                           warmup_epochs, min_lr, lr_milestones, lr_gamma)
     probe = GradDivergenceProbe(model.parameters()) if probe_divergence else None
 
     prof = StepProfiler(ctx.device if ctx.is_gpu else None)
@@ -415,14 +447,19 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
             mem_samples.append(mem)
 
             x, y = _to_device(x, y, ctx, augmenter)
+            if sched is not None:  # same table the flat engine indexes
+                lr_t = sched.lr_at(epoch * len(loader) + step)
+                for group in optimizer.param_groups:
+                    group["lr"] = lr_t
             with prof.compute():
                 optimizer.zero_grad(set_to_none=True)
                 logits = ddp(x)
                 if logits.is_cuda:
                     from ..models._functional_gpu import cross_entropy
-                    loss = cross_entropy(logits, y)
+                    loss = cross_entropy(logits, y, label_smoothing)
                 else:
-                    loss = F.cross_entropy(logits.float(), y)
+                    loss = F.cross_entropy(logits.float(), y,
+                                           label_smoothing=label_smoothing)
                 loss.backward()
             with prof.comm():
                 ddp.finalize_backward()
@@ -473,13 +510,19 @@ def dp_worker(rank: int, world_size: int, epochs: int, sample_size: int,
               optimizer_name: str = "adam", engine: str = "auto",
               checkpoint_path: Optional[str] = None,
               per_step_barrier: bool = False,
-              augment: bool = False, augment_pad: int = 4):
+              augment: bool = False, augment_pad: int = 4,
+              lr_schedule: str = "constant", warmup_epochs: float = 0.0,
+              min_lr: float = 0.0, lr_milestones=(), lr_gamma: float = 0.1,
+              weight_decay: float = 0.0, nesterov: bool = False,
+              decoupled_wd: bool = False, label_smoothing: float = 0.0):
     """Spawned worker entry (reference ``data_parallel_train.py:192-230``).
 
     ``engine``: ``flat`` (default on GPU via ``auto``) runs the hipGraph /
     fused-step fast path; ``eager`` the bucketed-DDP torch-optimizer loop.
     ``checkpoint_path``: save per epoch (rank 0) and resume when the file
-    exists — an extension over the reference."""
+    exists — an extension over the reference.
+    The schedule / weight-decay / Nesterov / AdamW / label-smoothing knobs
+    go to whichever engine runs (see ``train_dp_flat``)."""
     ctx = setup_distributed(rank, world_size, port, backend=backend)
     try:
         if ctx.is_gpu and model_name.startswith("resnet"):
@@ -494,7 +537,12 @@ def dp_worker(rank: int, world_size: int, epochs: int, sample_size: int,
                           optimizer_name=optimizer_name,
                           checkpoint_path=checkpoint_path,
                           per_step_barrier=per_step_barrier,
-                          augment=augment, augment_pad=augment_pad)
+                          augment=augment, augment_pad=augment_pad,
+                          lr_schedule=lr_schedule, warmup_epochs=warmup_epochs,
+                          min_lr=min_lr, lr_milestones=lr_milestones,
+                          lr_gamma=lr_gamma, weight_decay=weight_decay,
+                          nesterov=nesterov, decoupled_wd=decoupled_wd,
+                          label_smoothing=label_smoothing)
         else:
             train_dp(ctx, epochs, sample_size, logs_dir,
                      batch_size=batch_size, model_name=model_name,
@@ -502,6 +550,11 @@ def dp_worker(rank: int, world_size: int, epochs: int, sample_size: int,
                      optimizer_name=optimizer_name,
                      checkpoint_path=checkpoint_path,
                      per_step_barrier=per_step_barrier,
-                     augment=augment, augment_pad=augment_pad)
+                     augment=augment, augment_pad=augment_pad,
+                     lr_schedule=lr_schedule, warmup_epochs=warmup_epochs,
+                     min_lr=min_lr, lr_milestones=lr_milestones,
+                     lr_gamma=lr_gamma, weight_decay=weight_decay,
+                     nesterov=nesterov, decoupled_wd=decoupled_wd,
+                     label_smoothing=label_smoothing)
     finally:
         teardown_distributed(ctx)

@@ -94,19 +94,37 @@ class FlatParamManager:
         self.grad.zero_()
 
 
+def _sched_buffers(schedule, dev):
+    """Device residents of a scheduled optimizer: the f32 lr table the kernel
+    indexes with its step counter, and the scalar it records the lr in."""
+    if schedule is None:
+        return None, None
+    return schedule.table().to(dev), torch.zeros(1, device=dev)
+
+
 class HorizonAdam:
     """Fused flat-buffer Adam (K9): 1 elementwise kernel + step increment +
-    batched RSCK permute per step; zero_grad folded in."""
+    batched RSCK permute per step; zero_grad folded in.
+
+    ``schedule`` (an ``LRSchedule``): the learning rate of update ``t`` is
+    read on the device from the schedule's table, indexed by ``step_t`` — a
+    captured step walks the schedule under graph replay, and ``lr`` is
+    unused.  ``decoupled_wd``: AdamW (``w *= 1 - lr*wd`` instead of
+    ``g += wd*w``).  With neither, ``step`` launches ``k_adam_step`` as
+    before."""
 
     def __init__(self, mgr: FlatParamManager, lr: float = 1e-3,
                  betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 0.0):
+                 weight_decay: float = 0.0, schedule=None,
+                 decoupled_wd: bool = False):
         self.mgr = mgr
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
+        self.schedule, self.decoupled = schedule, bool(decoupled_wd)
         dev = mgr.master.device
         self.m = torch.zeros_like(mgr.master)
         self.v = torch.zeros_like(mgr.master)
         self.step_t = torch.zeros(1, device=dev)
+        self.lr_table, self.lr_out = _sched_buffers(schedule, dev)
 
     def step(self, zero_grad: bool = True, grad_bf16=None,
              grad_scale: float = 1.0, probe=None):
@@ -115,15 +133,37 @@ class HorizonAdam:
         ``probe``: optional ``(prev, sumsq, out)`` f32 tensors — the
         grad-divergence probe fused into the Adam pass (the standalone
         kernel costs a 3×|grad| extra sweep per step)."""
-        _ops.extension().flush_wgrad()  # batched deferred weight grads
+        ext = _ops.extension()
+        ext.flush_wgrad()  # batched deferred weight grads
         p0, p1, p2 = probe if probe is not None else (None, None, None)
-        _ops.extension().adam_step(self.mgr.master, self.mgr.grad, self.m,
-                                   self.v, self.mgr.shadow, self.step_t,
-                                   self.lr, self.betas[0], self.betas[1],
-                                   self.eps, self.wd, zero_grad,
-                                   self.mgr.stats_arena, grad_bf16,
-                                   grad_scale, p0, p1, p2)
+        if self.schedule is None and not self.decoupled:
+            ext.adam_step(self.mgr.master, self.mgr.grad, self.m,
+                          self.v, self.mgr.shadow, self.step_t,
+                          self.lr, self.betas[0], self.betas[1],
+                          self.eps, self.wd, zero_grad,
+                          self.mgr.stats_arena, grad_bf16,
+                          grad_scale, p0, p1, p2)
+        else:
+            ext.adam_step_sched(self.mgr.master, self.mgr.grad, self.m,
+                                self.v, self.mgr.shadow, self.step_t,
+                                self.lr_table, self.lr_out, self.lr,
+                                self.betas[0], self.betas[1], self.eps,
+                                self.wd, self.decoupled, zero_grad,
+                                self.mgr.stats_arena, grad_bf16, grad_scale,
+                                p0, p1, p2)
         self.mgr.refresh_rsck()
+
+    def current_lr(self) -> float:
+        """The learning rate the last update used.  Syncs — not for the hot
+        loop."""
+        if self.lr_out is None:
+            return float(self.lr)
+        return float(self.lr_out.cpu())
+
+    def set_step(self, n: int):
+        """Position the update counter: the next ``step`` is update ``n``
+        (0-based) — it reads ``lr_at(n)`` and bias-corrects with ``n + 1``."""
+        self.step_t.fill_(float(n))
 
     # -- checkpoint round-trip (utils/checkpoint.py) ----------------------
     def state_dict(self):
@@ -142,36 +182,78 @@ class HorizonAdam:
 
 
 class HorizonSGD:
+    """Fused flat-buffer SGD.  ``schedule``: as for ``HorizonAdam``; SGD then
+    owns an f32 device ``step_t``, bumped by a one-thread kernel in front of
+    the update (one added dispatch per step).  ``nesterov``: torch's
+    definition (``w -= lr*(g + mu*u)``).  With neither, ``step`` launches
+    ``k_sgd_step`` alone as before."""
+
     def __init__(self, mgr: FlatParamManager, lr: float = 0.1,
-                 momentum: float = 0.9, weight_decay: float = 0.0):
+                 momentum: float = 0.9, weight_decay: float = 0.0,
+                 schedule=None, nesterov: bool = False):
+        if nesterov and not momentum > 0:
+            raise ValueError("nesterov needs momentum > 0")
         self.mgr = mgr
         self.lr, self.mu, self.wd = lr, momentum, weight_decay
+        self.schedule, self.nesterov = schedule, bool(nesterov)
         self.mom = (torch.zeros_like(mgr.master) if momentum > 0 else None)
+        dev = mgr.master.device
+        self.lr_table, self.lr_out = _sched_buffers(schedule, dev)
+        self.step_t = (torch.zeros(1, device=dev)
+                       if schedule is not None else None)
 
     def step(self, zero_grad: bool = True, grad_bf16=None,
              grad_scale: float = 1.0, probe=None):
         """``probe``: optional ``(prev, sumsq, out)`` — the divergence
         probe fused into the SGD pass, like HorizonAdam's."""
-        _ops.extension().flush_wgrad()  # batched deferred weight grads
+        ext = _ops.extension()
+        ext.flush_wgrad()  # batched deferred weight grads
         p0, p1, p2 = probe if probe is not None else (None, None, None)
-        _ops.extension().sgd_step(self.mgr.master, self.mgr.grad, self.mom,
-                                  self.mgr.shadow, self.lr, self.mu, self.wd,
-                                  zero_grad, grad_bf16, grad_scale,
-                                  p0, p1, p2)
+        if self.schedule is None and not self.nesterov:
+            ext.sgd_step(self.mgr.master, self.mgr.grad, self.mom,
+                         self.mgr.shadow, self.lr, self.mu, self.wd,
+                         zero_grad, grad_bf16, grad_scale,
+                         p0, p1, p2)
+        else:
+            ext.sgd_step_sched(self.mgr.master, self.mgr.grad, self.mom,
+                               self.mgr.shadow, self.step_t, self.lr_table,
+                               self.lr_out, self.lr, self.mu, self.wd,
+                               self.nesterov, zero_grad, grad_bf16,
+                               grad_scale, p0, p1, p2)
         self.mgr.stats_arena.zero_()
         self.mgr.refresh_rsck()
 
+    def current_lr(self) -> float:
+        """The learning rate the last update used.  Syncs — not for the hot
+        loop."""
+        if self.lr_out is None:
+            return float(self.lr)
+        return float(self.lr_out.cpu())
+
+    def set_step(self, n: int):
+        """Position the schedule: the next ``step`` is update ``n`` (0-based).
+        Without a schedule SGD keeps no counter and this does nothing."""
+        if self.step_t is not None:
+            self.step_t.fill_(float(n))
+
     def state_dict(self):
-        return {"kind": "horizon_sgd", "lr": self.lr, "momentum": self.mu,
-                "weight_decay": self.wd,
-                "mom": (self.mom.detach().cpu()
-                        if self.mom is not None else None)}
+        state = {"kind": "horizon_sgd", "lr": self.lr, "momentum": self.mu,
+                 "weight_decay": self.wd,
+                 "mom": (self.mom.detach().cpu()
+                         if self.mom is not None else None)}
+        if self.step_t is not None:
+            state["step_t"] = self.step_t.detach().cpu()
+        return state
 
     def load_state_dict(self, state):
         if state.get("kind") != "horizon_sgd":
             raise ValueError("checkpoint optimizer state is not HorizonSGD")
         if (state.get("mom") is None) != (self.mom is None):
             raise ValueError("momentum buffer mismatch with checkpoint")
-        if self.mom is not None:
-            with torch.no_grad():
+        with torch.no_grad():
+            if self.mom is not None:
                 self.mom.copy_(state["mom"].to(self.mom.device))
+            # older checkpoints carry no counter: it stays where the caller
+            # put it (set_step)
+            if self.step_t is not None and state.get("step_t") is not None:
+                self.step_t.copy_(state["step_t"].to(self.step_t.device))

@@ -207,23 +207,32 @@ def linear(x, mod):
 
 class CrossEntropyFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, target):
+    def forward(ctx, logits, target, label_smoothing=0.0):
         logits = logits.float().contiguous()
-        loss, dlogits = _C().cross_entropy_fwd_bwd(logits, target)
+        if label_smoothing == 0.0:
+            loss, dlogits = _C().cross_entropy_fwd_bwd(logits, target)
+        else:
+            loss, dlogits = _C().cross_entropy_ls_fwd_bwd(
+                logits, target, float(label_smoothing))
         ctx.save_for_backward(dlogits)
         return loss
 
     @staticmethod
     def backward(ctx, gout):
         (dlogits,) = ctx.saved_tensors
-        return dlogits * gout, None
+        return dlogits * gout, None, None
 
 
-def cross_entropy(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
-    """Fused log-softmax + NLL + grad on GPU; torch on CPU."""
+def cross_entropy(logits: torch.Tensor, target: torch.Tensor,
+                  label_smoothing: float = 0.0) -> torch.Tensor:
+    """Fused log-softmax + NLL + grad on GPU; torch on CPU.
+
+    ``label_smoothing`` = ε smooths the target to ``(1-ε)·onehot + ε/NC``
+    (``F.cross_entropy``'s definition); ε = 0 runs the one-hot kernel."""
     if logits.is_cuda:
-        return CrossEntropyFn.apply(logits, target)
-    return torch.nn.functional.cross_entropy(logits.float(), target)
+        return CrossEntropyFn.apply(logits, target, float(label_smoothing))
+    return torch.nn.functional.cross_entropy(
+        logits.float(), target, label_smoothing=float(label_smoothing))
 
 
 def _rsck(mod, w_bf16):

@@ -78,6 +78,16 @@ void launch_adam_step(float*, float*, float*, float*, void*, const float*,
 void launch_sgd_step(float*, float*, float*, void*, long, float, float, float,
                      int, const void*, float, float*, float*, float*,
                      hipStream_t);
+void launch_ce_ls_fwd_bwd(const float*, const long*, float*, float*, int, int,
+                          float, hipStream_t);
+void launch_adam_step_ex(float*, float*, float*, float*, void*, const float*,
+                         long, float, float, float, float, float, int, float*,
+                         long, const void*, float, float*, float*, float*,
+                         const float*, long, float*, int, hipStream_t);
+void launch_sgd_step_ex(float*, float*, float*, void*, long, float, float,
+                        float, int, const void*, float, float*, float*,
+                        float*, float*, const float*, long, float*, int,
+                        hipStream_t);
 void launch_permute_krsc_rsck(const void*, void*, const int*, int, int,
                               hipStream_t);
 void launch_grad_divergence(const float*, float*, float*, float*, long, int,
@@ -857,6 +867,23 @@ std::vector<Tensor> cross_entropy_fwd_bwd(Tensor logits, Tensor target) {
   return {loss, dlogits};
 }
 
+// Label-smoothed form; eps == 0 launches the one-hot kernels above.
+std::vector<Tensor> cross_entropy_ls_fwd_bwd(Tensor logits, Tensor target,
+                                             double eps) {
+  if (eps == 0.0) return cross_entropy_fwd_bwd(logits, target);
+  TORCH_CHECK(eps > 0.0 && eps <= 1.0,
+              "label_smoothing must be in [0, 1], got ", eps);
+  check_f32(logits, "logits");
+  TORCH_CHECK(target.scalar_type() == torch::kLong && target.is_contiguous());
+  int B = (int)logits.size(0), NC = (int)logits.size(1);
+  Tensor loss = at::zeros({}, logits.options());
+  Tensor dlogits = at::empty({B, NC}, logits.options());
+  launch_ce_ls_fwd_bwd(logits.data_ptr<float>(), target.data_ptr<long>(),
+                       loss.data_ptr<float>(), dlogits.data_ptr<float>(), B,
+                       NC, (float)eps, cur_stream());
+  return {loss, dlogits};
+}
+
 // ------------------------------------------------------------------ gemm ---
 Tensor gemm_bf16(Tensor a, Tensor b) {
   // C[M,N] = A[M,K] · B[N,K]^T
@@ -958,6 +985,113 @@ void sgd_step(Tensor master, Tensor grad, c10::optional<Tensor> mom,
                   probe_out.has_value() ? probe_out->data_ptr<float>()
                                         : nullptr,
                   cur_stream());
+}
+
+// Scheduled / extended forms (adam_step / sgd_step above are untouched and
+// keep launching k_adam_step / k_sgd_step).
+// lr_table (optional): f32 [T] on the GPU; the kernel reads
+// lr_table[min(step_t − 1, T − 1)] after the counter bump, so `lr` is only
+// used without a table.  lr_out (optional): f32 [1], receives the lr used.
+const float* sched_table(const c10::optional<Tensor>& lr_table,
+                         const Tensor& master, long* T) {
+  *T = 0;
+  if (!lr_table.has_value()) return nullptr;
+  check_f32(*lr_table, "lr_table");
+  TORCH_CHECK(lr_table->dim() == 1 && lr_table->numel() >= 1
+                  && lr_table->device() == master.device(),
+              "lr_table must be a non-empty 1-D tensor on master's device");
+  *T = lr_table->numel();
+  return lr_table->data_ptr<float>();
+}
+
+float* sched_scalar(const c10::optional<Tensor>& t, const Tensor& master,
+                    const char* name) {
+  if (!t.has_value()) return nullptr;
+  check_f32(*t, name);
+  TORCH_CHECK(t->numel() == 1 && t->device() == master.device(), name,
+              " must hold one element on master's device");
+  return t->data_ptr<float>();
+}
+
+void adam_step_sched(Tensor master, Tensor grad, Tensor m, Tensor v,
+                     c10::optional<Tensor> shadow, Tensor step_t,
+                     c10::optional<Tensor> lr_table,
+                     c10::optional<Tensor> lr_out, double lr, double b1,
+                     double b2, double eps, double wd, bool decoupled,
+                     bool zero_grad, c10::optional<Tensor> extra_zero,
+                     c10::optional<Tensor> grad_bf16, double grad_scale,
+                     c10::optional<Tensor> probe_prev,
+                     c10::optional<Tensor> probe_sumsq,
+                     c10::optional<Tensor> probe_out) {
+  check_f32(master, "master");
+  TORCH_CHECK(probe_prev.has_value() == probe_sumsq.has_value()
+                  && probe_prev.has_value() == probe_out.has_value(),
+              "probe tensors must be passed together");
+  TORCH_CHECK(grad.numel() == master.numel() && m.numel() == master.numel()
+                  && v.numel() == master.numel(),
+              "grad / m / v must match master's size");
+  long T = 0;
+  const float* table = sched_table(lr_table, master, &T);
+  float* out = sched_scalar(lr_out, master, "lr_out");
+  float* st = sched_scalar(step_t, master, "step_t");
+  launch_adam_step_ex(master.data_ptr<float>(), grad.data_ptr<float>(),
+                      m.data_ptr<float>(), v.data_ptr<float>(),
+                      shadow.has_value() ? shadow->data_ptr() : nullptr, st,
+                      master.numel(), (float)lr, (float)b1, (float)b2,
+                      (float)eps, (float)wd, zero_grad ? 1 : 0,
+                      extra_zero.has_value() ? extra_zero->data_ptr<float>()
+                                             : nullptr,
+                      extra_zero.has_value() ? extra_zero->numel() : 0,
+                      grad_bf16.has_value() ? grad_bf16->data_ptr() : nullptr,
+                      (float)grad_scale,
+                      probe_prev.has_value() ? probe_prev->data_ptr<float>()
+                                             : nullptr,
+                      probe_sumsq.has_value() ? probe_sumsq->data_ptr<float>()
+                                              : nullptr,
+                      probe_out.has_value() ? probe_out->data_ptr<float>()
+                                            : nullptr,
+                      table, T, out, decoupled ? 1 : 0, cur_stream());
+}
+
+void sgd_step_sched(Tensor master, Tensor grad, c10::optional<Tensor> mom,
+                    c10::optional<Tensor> shadow,
+                    c10::optional<Tensor> step_t,
+                    c10::optional<Tensor> lr_table,
+                    c10::optional<Tensor> lr_out, double lr, double mu,
+                    double wd, bool nesterov, bool zero_grad,
+                    c10::optional<Tensor> grad_bf16, double grad_scale,
+                    c10::optional<Tensor> probe_prev,
+                    c10::optional<Tensor> probe_sumsq,
+                    c10::optional<Tensor> probe_out) {
+  check_f32(master, "master");
+  TORCH_CHECK(probe_prev.has_value() == probe_sumsq.has_value()
+                  && probe_prev.has_value() == probe_out.has_value(),
+              "probe tensors must be passed together");
+  TORCH_CHECK(grad.numel() == master.numel()
+                  && (!mom.has_value() || mom->numel() == master.numel()),
+              "grad / mom must match master's size");
+  TORCH_CHECK(!nesterov || (mom.has_value() && mu > 0.0),
+              "nesterov needs a momentum buffer and momentum > 0");
+  long T = 0;
+  const float* table = sched_table(lr_table, master, &T);
+  TORCH_CHECK(table == nullptr || step_t.has_value(),
+              "lr_table needs the step_t device counter");
+  float* out = sched_scalar(lr_out, master, "lr_out");
+  float* st = sched_scalar(step_t, master, "step_t");
+  launch_sgd_step_ex(master.data_ptr<float>(), grad.data_ptr<float>(),
+                     mom.has_value() ? mom->data_ptr<float>() : nullptr,
+                     shadow.has_value() ? shadow->data_ptr() : nullptr,
+                     master.numel(), (float)lr, (float)mu, (float)wd,
+                     zero_grad ? 1 : 0,
+                     grad_bf16.has_value() ? grad_bf16->data_ptr() : nullptr,
+                     (float)grad_scale,
+                     probe_prev.has_value() ? probe_prev->data_ptr<float>()
+                                            : nullptr,
+                     probe_sumsq.has_value() ? probe_sumsq->data_ptr<float>()
+                                             : nullptr,
+                     probe_out.has_value() ? probe_out->data_ptr<float>()
+                                           : nullptr,
+                     st, table, T, out, nesterov ? 1 : 0, cur_stream());
 }
 
 void permute_krsc_rsck(Tensor src, Tensor dst, Tensor meta,
@@ -1131,6 +1265,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gemm_bf16", &gemm_bf16);
   m.def("adam_step", &adam_step);
   m.def("sgd_step", &sgd_step);
+  m.def("cross_entropy_ls_fwd_bwd", &cross_entropy_ls_fwd_bwd);
+  m.def("adam_step_sched", &adam_step_sched, py::arg("master"),
+        py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("shadow"),
+        py::arg("step_t"), py::arg("lr_table"), py::arg("lr_out"),
+        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
+        py::arg("wd"), py::arg("decoupled"), py::arg("zero_grad"),
+        py::arg("extra_zero") = py::none(), py::arg("grad_bf16") = py::none(),
+        py::arg("grad_scale") = 1.0, py::arg("probe_prev") = py::none(),
+        py::arg("probe_sumsq") = py::none(),
+        py::arg("probe_out") = py::none());
+  m.def("sgd_step_sched", &sgd_step_sched, py::arg("master"),
+        py::arg("grad"), py::arg("mom"), py::arg("shadow"), py::arg("step_t"),
+        py::arg("lr_table"), py::arg("lr_out"), py::arg("lr"), py::arg("mu"),
+        py::arg("wd"), py::arg("nesterov"), py::arg("zero_grad"),
+        py::arg("grad_bf16") = py::none(), py::arg("grad_scale") = 1.0,
+        py::arg("probe_prev") = py::none(),
+        py::arg("probe_sumsq") = py::none(),
+        py::arg("probe_out") = py::none());
   m.def("permute_krsc_rsck", &permute_krsc_rsck);
   m.def("grad_divergence", &grad_divergence);
   m.def("normalize_u8", &normalize_u8);

@@ -1625,28 +1625,52 @@ __global__ __launch_bounds__(256) void k_linear_bwd_dw(
 }
 
 // ------------------------------------------------------- fused CE loss -----
-// Deterministic variant: ONE block, per-thread strided rows, ordered
-// block reduce of the loss (the default kernel's atomicAdd order varies).
-__global__ __launch_bounds__(256) void k_ce_fwd_bwd_det(
-    const float* __restrict__ logits, const long* __restrict__ target,
-    float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC) {
-  __shared__ float part[256];
-  float acc = 0.f;
-  for (int b = threadIdx.x; b < B; b += 256) {
-    const float* row = logits + (long)b * NC;
-    float mx = row[0];
-    for (int j = 1; j < NC; j++) mx = fmaxf(mx, row[j]);
-    float se = 0.f;
-    for (int j = 0; j < NC; j++) se += __expf(row[j] - mx);
-    float lse = __logf(se) + mx;
-    int t = (int)target[b];
-    acc += (lse - row[t]) / (float)B;
-    float invB = 1.f / (float)B;
+// One row of the fused loss: writes (softmax − target distribution)/B to
+// `drow` and returns the row's share of the mean loss.  LS=false is the
+// one-hot target; LS=true smooths it to (1−ε)·onehot + ε/NC, i.e.
+// loss = (1−ε)(lse − x_t) + ε(lse − mean_j x_j).  `eps` is dead code in the
+// LS=false instantiation, so the one-hot kernels are unchanged by it.
+template <bool LS>
+__device__ __forceinline__ float ce_row(const float* __restrict__ row, int t,
+                                        int B, int NC, float eps,
+                                        float* __restrict__ drow) {
+  float mx = row[0];
+  for (int j = 1; j < NC; j++) mx = fmaxf(mx, row[j]);
+  float se = 0.f;
+  for (int j = 0; j < NC; j++) se += __expf(row[j] - mx);
+  float lse = __logf(se) + mx;
+  float li = lse - row[t];
+  float invB = 1.f / (float)B;
+  if (LS) {
+    float sx = 0.f;
+    for (int j = 0; j < NC; j++) sx += row[j];
+    li = (1.f - eps) * li + eps * (lse - sx / (float)NC);
+    float on = 1.f - eps, off = eps / (float)NC;
     for (int j = 0; j < NC; j++) {
-      float pj = __expf(row[j] - lse);
-      dlogits[(long)b * NC + j] = (pj - (j == t ? 1.f : 0.f)) * invB;
+      float p = __expf(row[j] - lse);
+      drow[j] = (p - (j == t ? on : 0.f) - off) * invB;
+    }
+  } else {
+    for (int j = 0; j < NC; j++) {
+      float p = __expf(row[j] - lse);
+      drow[j] = (p - (j == t ? 1.f : 0.f)) * invB;
     }
   }
+  return li / (float)B;
+}
+
+// Deterministic variant: ONE block, per-thread strided rows, ordered
+// block reduce of the loss (the default kernel's atomicAdd order varies).
+template <bool LS>
+__device__ __forceinline__ void ce_det_body(
+    const float* __restrict__ logits, const long* __restrict__ target,
+    float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC,
+    float eps) {
+  __shared__ float part[256];
+  float acc = 0.f;
+  for (int b = threadIdx.x; b < B; b += 256)
+    acc += ce_row<LS>(logits + (long)b * NC, (int)target[b], B, NC, eps,
+                      dlogits + (long)b * NC);
   part[threadIdx.x] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -1658,25 +1682,45 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd_det(
 
 // logits[B,NC] f32 -> mean NLL loss (atomic into loss[0]) + dlogits f32
 // (softmax − onehot)/B.  One thread per row (NC ≤ 32).
+template <bool LS>
+__device__ __forceinline__ void ce_body(
+    const float* __restrict__ logits, const long* __restrict__ target,
+    float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC,
+    float eps, int b0, int bstride) {
+  for (int b = b0; b < B; b += bstride)
+    atomicAdd(loss, ce_row<LS>(logits + (long)b * NC, (int)target[b], B, NC,
+                               eps, dlogits + (long)b * NC));
+}
+
+__global__ __launch_bounds__(256) void k_ce_fwd_bwd_det(
+    const float* __restrict__ logits, const long* __restrict__ target,
+    float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC) {
+  ce_det_body<false>(logits, target, loss, dlogits, B, NC, 0.f);
+}
+
 __global__ __launch_bounds__(256) void k_ce_fwd_bwd(
     const float* __restrict__ logits, const long* __restrict__ target,
     float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC) {
-  for (int b = blockIdx.x * blockDim.x + threadIdx.x; b < B;
-       b += gridDim.x * blockDim.x) {
-    const float* row = logits + (long)b * NC;
-    float mx = row[0];
-    for (int j = 1; j < NC; j++) mx = fmaxf(mx, row[j]);
-    float se = 0.f;
-    for (int j = 0; j < NC; j++) se += __expf(row[j] - mx);
-    float lse = __logf(se) + mx;
-    int t = (int)target[b];
-    atomicAdd(loss, (lse - row[t]) / (float)B);
-    float invB = 1.f / (float)B;
-    for (int j = 0; j < NC; j++) {
-      float p = __expf(row[j] - lse);
-      dlogits[(long)b * NC + j] = (p - (j == t ? 1.f : 0.f)) * invB;
-    }
-  }
+  ce_body<false>(logits, target, loss, dlogits, B, NC, 0.f,
+                 blockIdx.x * blockDim.x + threadIdx.x,
+                 gridDim.x * blockDim.x);
+}
+
+// label-smoothed forms (ε > 0 only; ε = 0 launches the kernels above)
+__global__ __launch_bounds__(256) void k_ce_ls_fwd_bwd_det(
+    const float* __restrict__ logits, const long* __restrict__ target,
+    float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC,
+    float eps) {
+  ce_det_body<true>(logits, target, loss, dlogits, B, NC, eps);
+}
+
+__global__ __launch_bounds__(256) void k_ce_ls_fwd_bwd(
+    const float* __restrict__ logits, const long* __restrict__ target,
+    float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC,
+    float eps) {
+  ce_body<true>(logits, target, loss, dlogits, B, NC, eps,
+                blockIdx.x * blockDim.x + threadIdx.x,
+                gridDim.x * blockDim.x);
 }
 
 // ------------------------------------------------------- fused optimizers --
@@ -1691,21 +1735,26 @@ __global__ __launch_bounds__(256) void k_ce_fwd_bwd(
 // (measured ~61 µs/step standalone vs ~13 µs marginal here; engine-flat
 // trace r02).  The probe always reads the LOCAL f32 grad (pre-average),
 // matching the reference's per-worker probe semantics.
-__global__ __launch_bounds__(256) void k_adam_step(
+// The loop lives in adam_body / sgd_body (grid-stride start and stride are
+// formed in the kernel and passed in) so that k_adam_step / k_sgd_step
+// (lr by value) and the *_ex kernels (lr from a device table, AdamW,
+// Nesterov) evaluate one update expression with one contraction.
+// DECOUPLED (AdamW): wd is not added to g; w is scaled by (1 − lr·wd) before
+// the Adam update, as torch.optim.AdamW does.
+template <bool DECOUPLED>
+__device__ __forceinline__ void adam_body(
     float* __restrict__ master, float* __restrict__ grad,
     float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ shadow,
     const float* __restrict__ step_t, long n, float lr, float b1, float b2,
     float eps, float wd, int zero_grad, float* __restrict__ extra_zero,
     long n_extra, const bf16* __restrict__ gsrc, float gscale,
-    float* __restrict__ prev, float* __restrict__ sumsq) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n_extra;
-       i += (long)gridDim.x * blockDim.x)
-    extra_zero[i] = 0.f;
+    float* __restrict__ prev, float* __restrict__ sumsq, long i0,
+    long istride) {
+  for (long i = i0; i < n_extra; i += istride) extra_zero[i] = 0.f;
   float t = step_t[0];
   float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
   float acc = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
+  for (long i = i0; i < n; i += istride) {
     float gl = grad[i];
     float g = gsrc != nullptr ? b2f(gsrc[i]) * gscale : gl;
     if (prev != nullptr) {
@@ -1714,7 +1763,11 @@ __global__ __launch_bounds__(256) void k_adam_step(
       acc += d * d;
     }
     float w = master[i];
-    if (wd != 0.f) g += wd * w;
+    if (DECOUPLED) {
+      if (wd != 0.f) w *= 1.f - lr * wd;
+    } else {
+      if (wd != 0.f) g += wd * w;
+    }
     float mi = b1 * m[i] + (1.f - b1) * g;
     float vi = b2 * v[i] + (1.f - b2) * g * g;
     m[i] = mi;
@@ -1734,17 +1787,19 @@ __global__ __launch_bounds__(256) void k_adam_step(
   }
 }
 
-__global__ __launch_bounds__(256) void k_sgd_step(
+// NESTEROV: u = μ·mom + g; mom = u; w −= lr·(g + μ·u)  (torch's definition)
+template <bool NESTEROV>
+__device__ __forceinline__ void sgd_body(
     float* __restrict__ master, float* __restrict__ grad,
     float* __restrict__ mom, bf16* __restrict__ shadow, long n, float lr,
     float mu, float wd, int zero_grad, const bf16* __restrict__ gsrc,
-    float gscale, float* __restrict__ prev, float* __restrict__ sumsq) {
+    float gscale, float* __restrict__ prev, float* __restrict__ sumsq,
+    long i0, long istride) {
   float acc = 0.f;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-       i += (long)gridDim.x * blockDim.x) {
+  for (long i = i0; i < n; i += istride) {
     float gl = grad[i];
     float g = gsrc != nullptr ? b2f(gsrc[i]) * gscale : gl;
-    if (prev != nullptr) {  // fused divergence probe (see k_adam_step)
+    if (prev != nullptr) {  // fused divergence probe (see adam_body)
       float d = gl - prev[i];
       prev[i] = gl;
       acc += d * d;
@@ -1753,7 +1808,10 @@ __global__ __launch_bounds__(256) void k_sgd_step(
     if (wd != 0.f) g += wd * w;
     float u = (mom != nullptr) ? (mu * mom[i] + g) : g;
     if (mom != nullptr) mom[i] = u;
-    w -= lr * u;
+    if (NESTEROV)
+      w -= lr * (g + mu * u);
+    else
+      w -= lr * u;
     master[i] = w;
     if (shadow != nullptr) shadow[i] = f2b(w);
     if (zero_grad) grad[i] = 0.f;
@@ -1766,6 +1824,83 @@ __global__ __launch_bounds__(256) void k_sgd_step(
     if (threadIdx.x == 0)
       atomicAdd(sumsq, ws[0] + ws[1] + ws[2] + ws[3]);
   }
+}
+
+// Learning rate of this update for the *_ex kernels: with a table,
+// lr_table[clamp(step_t − 1, 0, T−1)] — `step_t` is the already-incremented
+// f32 device counter, so a replayed hipGraph walks the schedule with no host
+// work; without one, the by-value `lr`.  Wave-uniform: one 4-byte load per
+// thread, before the loop.  Thread 0 of block 0 records the value used.
+__device__ __forceinline__ float sched_lr(const float* __restrict__ step_t,
+                                          const float* __restrict__ lr_table,
+                                          long T, float lr,
+                                          float* __restrict__ lr_out) {
+  if (lr_table != nullptr) {
+    long k = (long)step_t[0] - 1;
+    k = k < 0 ? 0 : (k > T - 1 ? T - 1 : k);
+    lr = lr_table[k];
+  }
+  if (lr_out != nullptr && blockIdx.x == 0 && threadIdx.x == 0)
+    lr_out[0] = lr;
+  return lr;
+}
+
+__global__ __launch_bounds__(256) void k_adam_step(
+    float* __restrict__ master, float* __restrict__ grad,
+    float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ shadow,
+    const float* __restrict__ step_t, long n, float lr, float b1, float b2,
+    float eps, float wd, int zero_grad, float* __restrict__ extra_zero,
+    long n_extra, const bf16* __restrict__ gsrc, float gscale,
+    float* __restrict__ prev, float* __restrict__ sumsq) {
+  adam_body<false>(master, grad, m, v, shadow, step_t, n, lr, b1, b2, eps,
+                   wd, zero_grad, extra_zero, n_extra, gsrc, gscale, prev,
+                   sumsq,
+                   (long)blockIdx.x * blockDim.x + threadIdx.x,
+                   (long)gridDim.x * blockDim.x);
+}
+
+template <bool DECOUPLED>
+__global__ __launch_bounds__(256) void k_adam_step_ex(
+    float* __restrict__ master, float* __restrict__ grad,
+    float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ shadow,
+    const float* __restrict__ step_t, long n, float lr, float b1, float b2,
+    float eps, float wd, int zero_grad, float* __restrict__ extra_zero,
+    long n_extra, const bf16* __restrict__ gsrc, float gscale,
+    float* __restrict__ prev, float* __restrict__ sumsq,
+    const float* __restrict__ lr_table, long T, float* __restrict__ lr_out) {
+  lr = sched_lr(step_t, lr_table, T, lr, lr_out);
+  adam_body<DECOUPLED>(master, grad, m, v, shadow, step_t, n, lr, b1, b2,
+                       eps, wd, zero_grad, extra_zero, n_extra, gsrc, gscale,
+                       prev, sumsq,
+                       (long)blockIdx.x * blockDim.x + threadIdx.x,
+                       (long)gridDim.x * blockDim.x);
+}
+
+__global__ __launch_bounds__(256) void k_sgd_step(
+    float* __restrict__ master, float* __restrict__ grad,
+    float* __restrict__ mom, bf16* __restrict__ shadow, long n, float lr,
+    float mu, float wd, int zero_grad, const bf16* __restrict__ gsrc,
+    float gscale, float* __restrict__ prev, float* __restrict__ sumsq) {
+  sgd_body<false>(master, grad, mom, shadow, n, lr, mu, wd, zero_grad, gsrc,
+                  gscale, prev, sumsq,
+                  (long)blockIdx.x * blockDim.x + threadIdx.x,
+                  (long)gridDim.x * blockDim.x);
+}
+
+// `step_t` may be null only when `lr_table` is (unscheduled Nesterov).
+template <bool NESTEROV>
+__global__ __launch_bounds__(256) void k_sgd_step_ex(
+    float* __restrict__ master, float* __restrict__ grad,
+    float* __restrict__ mom, bf16* __restrict__ shadow, long n, float lr,
+    float mu, float wd, int zero_grad, const bf16* __restrict__ gsrc,
+    float gscale, float* __restrict__ prev, float* __restrict__ sumsq,
+    const float* __restrict__ step_t, const float* __restrict__ lr_table,
+    long T, float* __restrict__ lr_out) {
+  lr = sched_lr(step_t, lr_table, T, lr, lr_out);
+  sgd_body<NESTEROV>(master, grad, mom, shadow, n, lr, mu, wd, zero_grad,
+                     gsrc, gscale, prev, sumsq,
+                     (long)blockIdx.x * blockDim.x + threadIdx.x,
+                     (long)gridDim.x * blockDim.x);
 }
 
 __global__ void k_inc_step(float* step_t) { step_t[0] += 1.f; }
@@ -2553,6 +2688,17 @@ void launch_ce_fwd_bwd(const float* logits, const long* target, float* loss,
                                          NC);
 }
 
+void launch_ce_ls_fwd_bwd(const float* logits, const long* target,
+                          float* loss, float* dlogits, int B, int NC,
+                          float eps, hipStream_t st) {
+  if (g_det_kernels)
+    k_ce_ls_fwd_bwd_det<<<1, 256, 0, st>>>(logits, target, loss, dlogits, B,
+                                           NC, eps);
+  else
+    k_ce_ls_fwd_bwd<<<gsz(B), 256, 0, st>>>(logits, target, loss, dlogits, B,
+                                            NC, eps);
+}
+
 void launch_adam_step(float* master, float* grad, float* m, float* v,
                       void* shadow, const float* step_t, long n, float lr,
                       float b1, float b2, float eps, float wd, int zero_grad,
@@ -2576,6 +2722,45 @@ void launch_sgd_step(float* master, float* grad, float* mom, void* shadow,
   k_sgd_step<<<gsz(n), 256, 0, st>>>(master, grad, mom, (bf16*)shadow, n, lr,
                                      mu, wd, zero_grad, (const bf16*)gsrc,
                                      gscale, prev, sumsq);
+  if (prev != nullptr)
+    k_gdiv_finalize<<<1, 1, 0, st>>>(sumsq, divout, 0);
+}
+
+// Scheduled / extended forms.  Adam bumps its own step_t exactly as above
+// (no added dispatch); SGD bumps `step_t` with the same one-thread kernel
+// only when it has a table to index (two-launch scheme, see
+// k_augment_normalize_u8's counter).
+void launch_adam_step_ex(float* master, float* grad, float* m, float* v,
+                         void* shadow, const float* step_t, long n, float lr,
+                         float b1, float b2, float eps, float wd,
+                         int zero_grad, float* extra_zero, long n_extra,
+                         const void* gsrc, float gscale, float* prev,
+                         float* sumsq, float* divout, const float* lr_table,
+                         long T, float* lr_out, int decoupled,
+                         hipStream_t st) {
+  k_inc_step<<<1, 1, 0, st>>>((float*)step_t);
+#define LA(D) k_adam_step_ex<D><<<gsz(n), 256, 0, st>>>( \
+    master, grad, m, v, (bf16*)shadow, step_t, n, lr, b1, b2, eps, wd, \
+    zero_grad, extra_zero, n_extra, (const bf16*)gsrc, gscale, prev, sumsq, \
+    lr_table, T, lr_out)
+  if (decoupled) LA(true); else LA(false);
+#undef LA
+  if (prev != nullptr)
+    k_gdiv_finalize<<<1, 1, 0, st>>>(sumsq, divout, 0);
+}
+
+void launch_sgd_step_ex(float* master, float* grad, float* mom, void* shadow,
+                        long n, float lr, float mu, float wd, int zero_grad,
+                        const void* gsrc, float gscale, float* prev,
+                        float* sumsq, float* divout, float* step_t,
+                        const float* lr_table, long T, float* lr_out,
+                        int nesterov, hipStream_t st) {
+  if (lr_table != nullptr) k_inc_step<<<1, 1, 0, st>>>(step_t);
+#define LS(N) k_sgd_step_ex<N><<<gsz(n), 256, 0, st>>>( \
+    master, grad, mom, (bf16*)shadow, n, lr, mu, wd, zero_grad, \
+    (const bf16*)gsrc, gscale, prev, sumsq, step_t, lr_table, T, lr_out)
+  if (nesterov) LS(true); else LS(false);
+#undef LS
   if (prev != nullptr)
     k_gdiv_finalize<<<1, 1, 0, st>>>(sumsq, divout, 0);
 }
