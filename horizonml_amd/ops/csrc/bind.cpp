@@ -674,6 +674,20 @@ std::vector<Tensor> conv_bn_act_bwd(
 }
 
 // --------------------------------------------------------- depthwise conv --
+// The depthwise kernels keep the filter taps in a register array of
+// DW_MAXRS = 25 floats (elem_kernels.hip): a larger filter would index
+// past it, so it is refused here, before any launch.
+void check_dw_geometry(int R, int S, int64_t stride, int H, int W,
+                       int64_t pad) {
+  TORCH_CHECK(R >= 1 && S >= 1 && R * S <= 25,
+              "depthwise filter must have R*S <= 25 taps, got ", R, "x", S);
+  TORCH_CHECK(stride >= 1, "depthwise stride must be >= 1, got ", stride);
+  TORCH_CHECK(pad >= 0, "depthwise pad must be >= 0, got ", pad);
+  TORCH_CHECK(H + 2 * pad >= R && W + 2 * pad >= S,
+              "depthwise output must be at least 1x1: input ", H, "x", W,
+              ", pad ", pad, ", filter ", R, "x", S);
+}
+
 std::vector<Tensor> dw_conv_bn_fwd(
     Tensor x, Tensor w, Tensor gamma, Tensor beta, Tensor running_mean,
     Tensor running_var, int64_t stride, int64_t pad, double momentum,
@@ -686,6 +700,7 @@ std::vector<Tensor> dw_conv_bn_fwd(
       W = (int)x.size(3);
   int R = (int)w.size(0), S = (int)w.size(1);
   TORCH_CHECK((int)w.size(2) == C, "depthwise channel mismatch");
+  check_dw_geometry(R, S, stride, H, W, pad);
   int Ho = (H + 2 * (int)pad - R) / (int)stride + 1;
   int Wo = (W + 2 * (int)pad - S) / (int)stride + 1;
   long M = (long)Nb * Ho * Wo;
@@ -733,8 +748,16 @@ std::vector<Tensor> dw_conv_bn_bwd(
   check_cl(x, "x");
   int Nb = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
       W = (int)x.size(3);
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 &&
+                  w.is_contiguous() && w.dim() == 3 && w.size(2) == C,
+              "w must be contiguous bf16 [R,S,C] with C = x channels");
   int R = (int)w.size(0), S = (int)w.size(1);
+  check_dw_geometry(R, S, stride, H, W, pad);
   int Ho = (int)dy.size(2), Wo = (int)dy.size(3);
+  TORCH_CHECK(dy.size(0) == Nb && dy.size(1) == C &&
+                  Ho == (H + 2 * (int)pad - R) / (int)stride + 1 &&
+                  Wo == (W + 2 * (int)pad - S) / (int)stride + 1,
+              "dy shape does not match the depthwise output of x");
   long M = (long)Nb * Ho * Wo;
   auto fopt = x.options().dtype(torch::kFloat32);
   auto st = cur_stream();
@@ -820,12 +843,25 @@ Tensor avgpool_bwd(Tensor dy, int64_t H, int64_t W) {
 Tensor linear_fwd(Tensor x, Tensor w, c10::optional<Tensor> bias) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
               x.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(w.is_contiguous() && w.scalar_type() == torch::kBFloat16);
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
+                  w.scalar_type() == torch::kBFloat16,
+              "w must be contiguous bf16 on GPU");
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2,
+              "linear_fwd: x must be [B, In] and w [Out, In], got ", x.dim(),
+              "-D x and ", w.dim(), "-D w");
   int B = (int)x.size(0), In = (int)x.size(1), Out = (int)w.size(0);
+  TORCH_CHECK(w.size(1) == In, "linear_fwd: w has ", w.size(1),
+              " input columns, x has ", In);
+  // k_linear_fwd reads x and w as vec8 chunks, at most 4 per lane
+  TORCH_CHECK(In % 8 == 0, "linear_fwd: In must be a multiple of 8, got ",
+              In);
+  TORCH_CHECK(In <= 2048, "linear_fwd: In must be <= 2048, got ", In);
   Tensor y = at::empty({B, Out}, x.options().dtype(torch::kFloat32));
   const float* bptr = nullptr;
   if (bias.has_value()) {
     check_f32(*bias, "bias");
+    TORCH_CHECK(bias->numel() == Out, "linear_fwd: bias has ", bias->numel(),
+                " elements, Out is ", Out);
     bptr = bias->data_ptr<float>();
   }
   launch_linear_fwd(x.data_ptr(), w.data_ptr(), bptr, y.data_ptr<float>(), B,
@@ -837,7 +873,29 @@ std::vector<Tensor> linear_bwd(Tensor dy, Tensor x, Tensor w, bool need_dx,
                                bool need_db, c10::optional<Tensor> dw_out,
                                c10::optional<Tensor> db_out) {
   check_f32(dy, "dy");
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() &&
+                  x.scalar_type() == torch::kBFloat16 && x.dim() == 2,
+              "linear_bwd: x must be contiguous bf16 [B, In] on GPU");
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() &&
+                  w.scalar_type() == torch::kBFloat16 && w.dim() == 2,
+              "linear_bwd: w must be contiguous bf16 [Out, In] on GPU");
   int B = (int)x.size(0), In = (int)x.size(1), Out = (int)w.size(0);
+  TORCH_CHECK(w.size(1) == In, "linear_bwd: w has ", w.size(1),
+              " input columns, x has ", In);
+  TORCH_CHECK(dy.dim() == 2 && dy.size(0) == B && dy.size(1) == Out,
+              "linear_bwd: dy must be [B, Out] = [", B, ", ", Out, "]");
+  if (dw_out.has_value()) {
+    check_f32(*dw_out, "dw_out");
+    TORCH_CHECK(dw_out->dim() == 2 && dw_out->size(0) == Out &&
+                    dw_out->size(1) == In,
+                "linear_bwd: dw_out must be [Out, In] = [", Out, ", ", In,
+                "]");
+  }
+  if (db_out.has_value()) {
+    check_f32(*db_out, "db_out");
+    TORCH_CHECK(db_out->numel() == Out, "linear_bwd: db_out has ",
+                db_out->numel(), " elements, Out is ", Out);
+  }
   auto fopt = x.options().dtype(torch::kFloat32);
   bool direct = dw_out.has_value();
   Tensor dx, dw = direct ? *dw_out : at::empty({Out, In}, fopt);

@@ -1288,8 +1288,8 @@ __global__ __launch_bounds__(256) void k_maxpool_fwd_v8(
     int barg[8];
 #pragma unroll
     for (int e = 0; e < 8; e++) {
-      best[e] = -1e30f;
-      barg[e] = 0;
+      best[e] = 0.f;
+      barg[e] = -1;  // none yet: the first in-bounds tap always wins
     }
     for (int r = 0; r < 3; r++) {
       int hi = ho * 2 - 1 + r;
@@ -1303,7 +1303,7 @@ __global__ __launch_bounds__(256) void k_maxpool_fwd_v8(
 #pragma unroll
         for (int e = 0; e < 8; e++) {
           float val = b2f(xv.e[e]);
-          if (val > best[e]) {
+          if (barg[e] < 0 || val > best[e]) {
             best[e] = val;
             barg[e] = r * 3 + sp;
           }
@@ -1368,6 +1368,9 @@ __global__ __launch_bounds__(256) void k_maxpool_bwd_v8(
 // ----------------------------------------------------------------- pooling --
 
 // 3x3/2 pad1 max-pool, NHWC; argmax index (0..8) saved as u8 for backward.
+// The result is the first maximum in (r,s) scan order among the in-bounds
+// taps, for any finite input (the centre tap is always in bounds).  NaN and
+// ±inf inputs are not supported: this file is built with -ffast-math.
 __global__ __launch_bounds__(256) void k_maxpool_fwd(
     const bf16* __restrict__ x, bf16* __restrict__ y,
     unsigned char* __restrict__ idx, int Nb, int H, int W, int C, int Hp,
@@ -1381,8 +1384,8 @@ __global__ __launch_bounds__(256) void k_maxpool_fwd(
     t /= Wp;
     int ho = (int)(t % Hp);
     int n = (int)(t / Hp);
-    float best = -1e30f;
-    int barg = 0;
+    float best = 0.f;
+    int barg = -1;  // none yet: the first in-bounds tap always wins
     for (int r = 0; r < 3; r++) {
       int hi = ho * 2 - 1 + r;
       if (hi < 0 || hi >= H) continue;
@@ -1390,7 +1393,7 @@ __global__ __launch_bounds__(256) void k_maxpool_fwd(
         int wi = wo * 2 - 1 + s;
         if (wi < 0 || wi >= W) continue;
         float v = b2f(x[((long)(n * H + hi) * W + wi) * C + c]);
-        if (v > best) {
+        if (barg < 0 || v > best) {
           best = v;
           barg = r * 3 + s;
         }
