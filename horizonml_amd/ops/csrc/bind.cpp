@@ -8,109 +8,7 @@
 #include <memory>
 #include <vector>
 
-struct ConvP {
-  int Nb, H, W, C, K;
-  int Ho, Wo, R, S;
-  int str, pad;
-  int M, Kd;
-};
-
-extern "C" {
-int conv_fwd_splitk(ConvP);
-int conv_dgrad_splitk(ConvP);
-void launch_conv_fwd(const void*, const void*, void*, float*, ConvP,
-                     hipStream_t);
-void launch_conv_fwd_splitk(const void*, const void*, float*, ConvP, int,
-                            hipStream_t);
-void launch_conv_dgrad(const void*, const void*, void*, float*, int, ConvP,
-                       int, hipStream_t);
-void launch_gemm_bf16(const void*, const void*, void*, int, int, int,
-                      hipStream_t);
-int wgrad_msplit(ConvP);
-void launch_wgrad(const void*, const void*, float*, float*, ConvP,
-                  hipStream_t);
-void launch_wgrad_batched_t(const void*, int, int, int, hipStream_t);
-void launch_wgrad_reduce_batched(const void*, int, hipStream_t);
-void launch_bn_apply(const void*, const void*, void*, const float*,
-                     const float*, const float*, float*, float*, float*,
-                     float*, long, int, float, float, int, int, hipStream_t);
-void launch_bn_apply_f32(const float*, const void*, void*, void*,
-                         const float*, const float*, const float*, float*,
-                         float*, float*, float*, long, int, float, float,
-                         int, int, int, hipStream_t);
-void launch_stats_reduce(const float*, float*, long, int, int, hipStream_t);
-void launch_cast_f32_bf16(const float*, void*, long, int, int, hipStream_t);
-void set_kernels_deterministic(int);
-void launch_stats_bf16_det(const void*, float*, long, int, hipStream_t);
-void launch_cast_bnact(const float*, void*, long, int, int, int, const void*,
-                       const void*, const float*, const float*, const float*,
-                       const float*, float*, float*, int, hipStream_t);
-void launch_bnact_bwd_reduce(const void*, const void*, const void*,
-                             const float*, const float*, const float*,
-                             const float*, float*, float*, long, int, int,
-                             hipStream_t);
-void launch_bn_bwd_apply(const void*, const void*, const void*, const float*,
-                         const float*, const float*, const float*,
-                         const float*, const float*, void*, void*, long, int,
-                         int, hipStream_t);
-void launch_dw_fwd(const void*, const void*, void*, float*, int, int, int,
-                   int, int, int, int, int, int, int, hipStream_t);
-void launch_dw_dgrad(const void*, const void*, void*, int, int, int, int,
-                     int, int, int, int, int, int, hipStream_t);
-void launch_dw_wgrad(const void*, const void*, float*, int, int, int, int,
-                     int, int, int, int, int, int, hipStream_t);
-void launch_maxpool_fwd(const void*, void*, unsigned char*, int, int, int,
-                        int, int, int, hipStream_t);
-void launch_maxpool_bwd(const void*, const unsigned char*, void*, int, int,
-                        int, int, int, int, hipStream_t);
-void launch_avgpool_fwd(const void*, void*, int, int, int, hipStream_t);
-void launch_avgpool_bwd(const void*, void*, int, int, int, hipStream_t);
-void launch_linear_fwd(const void*, const void*, const float*, float*, int,
-                       int, int, hipStream_t);
-void launch_linear_bwd(const float*, const void*, const void*, void*, float*,
-                       float*, int, int, int, int, hipStream_t);
-void launch_ce_fwd_bwd(const float*, const long*, float*, float*, int, int,
-                       hipStream_t);
-void launch_adam_step(float*, float*, float*, float*, void*, const float*,
-                      long, float, float, float, float, float, int, float*,
-                      long, const void*, float, float*, float*, float*,
-                      hipStream_t);
-void launch_sgd_step(float*, float*, float*, void*, long, float, float, float,
-                     int, const void*, float, float*, float*, float*,
-                     hipStream_t);
-void launch_ce_ls_fwd_bwd(const float*, const long*, float*, float*, int, int,
-                          float, hipStream_t);
-void launch_adam_step_ex(float*, float*, float*, float*, void*, const float*,
-                         long, float, float, float, float, float, int, float*,
-                         long, const void*, float, float*, float*, float*,
-                         const float*, long, float*, int, hipStream_t);
-void launch_sgd_step_ex(float*, float*, float*, void*, long, float, float,
-                        float, int, const void*, float, float*, float*,
-                        float*, float*, const float*, long, float*, int,
-                        hipStream_t);
-void launch_permute_krsc_rsck(const void*, void*, const int*, int, int,
-                              hipStream_t);
-void launch_grad_divergence(const float*, float*, float*, float*, long, int,
-                            hipStream_t);
-void launch_normalize_u8(const void*, void*, long, int, long, float, float,
-                         hipStream_t);
-void launch_augment_normalize_u8(const void*, void*, void*, const int*, long,
-                                 int, int, int, int, int, float, float,
-                                 hipStream_t);
-void set_kernels_bn_owner(int);
-int kernels_bn_owner();
-void bn_owner_launch_counts(long*, long*);
-int bn_owner_fwd_pick(long, int, int);
-int bn_owner_bwd_pick(long, int, int);
-void launch_bn_fwd_owner(const float*, const void*, void*, void*,
-                         const float*, const float*, float*, float*, float*,
-                         float*, long, int, float, float, int, int, int,
-                         hipStream_t);
-void launch_bn_bwd_owner(const void*, const void*, const void*, const float*,
-                         const float*, const float*, const float*, float*,
-                         float*, void*, void*, long, int, int, int,
-                         hipStream_t);
-}
+#include "launch.h"  // ABI structs, launcher declarations, env_long
 
 namespace {
 
@@ -153,62 +51,6 @@ std::vector<int64_t> bn_owner_launches() {
 // 2 launches instead of ~40, full chip occupancy, no atomics.  Task tables
 // travel as kernel arguments by value, so the path is hipGraph-capture-safe
 // (no host staging buffers whose contents could change between replays).
-constexpr int WG_MAX_TASKS = 20;
-
-struct MagicP {
-  unsigned m[4];
-  int s[4];
-  unsigned d[4];
-};
-
-static void magic_u32_h(unsigned d, unsigned* m, int* sh) {
-  if (d <= 1) { *m = 0; *sh = 0; return; }
-  int p = 0;
-  while ((1ull << p) < d) p++;
-  *m = (unsigned)((((unsigned long long)((1ull << p) - d) << 32) / d) + 1);
-  *sh = p;
-}
-
-static MagicP make_magic_mode1(const ConvP& p) {
-  MagicP mg{};
-  unsigned d[4] = {(unsigned)(p.Ho * p.Wo), (unsigned)p.Wo,
-                   (unsigned)(p.S * p.C), (unsigned)p.C};
-  for (int i = 0; i < 4; i++) {
-    mg.d[i] = d[i] ? d[i] : 1;
-    magic_u32_h(mg.d[i], &mg.m[i], &mg.s[i]);
-  }
-  return mg;
-}
-
-struct WgradTask {
-  const void* X;
-  const void* Dz;
-  float* out;
-  ConvP p;
-  MagicP mg;
-  int Ntot, mchunk, msplit, tx, ty;
-  int base;
-  int vec;
-};
-
-struct WgradBatchArgs {
-  int n;
-  WgradTask t[WG_MAX_TASKS];
-};
-
-struct WredTask {
-  const float* ws;
-  float* dW;
-  long n;
-  int msplit;
-  int base;
-};
-
-struct WredBatchArgs {
-  int n;
-  WredTask t[WG_MAX_TASKS];
-};
-
 struct PendingWgrad {
   torch::Tensor x, dconv, dw;
   ConvP p;
@@ -311,23 +153,15 @@ void flush_one_group(int group_lo, int group_hi) {
   // large-M tasks halves the Dz re-read; 128-wide ko for K>=128 tasks
   // halves the X re-read — separate launches keep per-class LDS/occupancy
   auto tk3_of = [](const ConvP& p) {
-    static int kd_min = [] {
-      const char* e = getenv("HZ_WG_TK3_KD");
-      return e ? atoi(e) : 256;  // swept on MI355X (r50 224 + bs1024)
-    }();
-    static int m_min = [] {
-      const char* e = getenv("HZ_WG_TK3_M");
-      // swept on MI355X: M=2048 admits CIFAR-bs64 layer1 (M=4096) and
-      // costs ~2% at the parity point; 5000 keeps r50@224 at 9.39 ms
-      return e ? atoi(e) : 5000;
-    }();
+    // swept on MI355X (r50 224 + bs1024)
+    static const int kd_min = (int)env_long("HZ_WG_TK3_KD", 256);
+    // swept on MI355X: M=2048 admits CIFAR-bs64 layer1 (M=4096) and
+    // costs ~2% at the parity point; 5000 keeps r50@224 at 9.39 ms
+    static const int m_min = (int)env_long("HZ_WG_TK3_M", 5000);
     return (p.Kd >= kd_min && p.M >= m_min) ? 128 : 64;
   };
   auto tko_of = [](const ConvP& p) {
-    static int k_min = [] {
-      const char* e = getenv("HZ_WG_TKO_K");
-      return e ? atoi(e) : 128;
-    }();
+    static const int k_min = (int)env_long("HZ_WG_TKO_K", 128);
     return p.K >= k_min ? 128 : 64;
   };
   for (int cls = 0; cls < 4; cls++) {
@@ -350,7 +184,7 @@ void flush_one_group(int group_lo, int group_hi) {
         t.out = msplit[i] > 1 ? ws_base + ws_off[i]
                               : pw.dw.data_ptr<float>();
         t.p = pw.p;
-        t.mg = make_magic_mode1(pw.p);
+        t.mg = make_magic(pw.p, 1);
         t.Ntot = pw.p.K;
         t.mchunk = mchunk[i];
         t.msplit = msplit[i];
@@ -400,6 +234,23 @@ void check_f32(const Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kFloat32 &&
                   t.is_contiguous(),
               name, " must be contiguous f32 on GPU");
+}
+
+// data pointer of an optional tensor, nullptr when absent
+template <class T>
+T* opt_ptr(const c10::optional<Tensor>& t) {
+  return t.has_value() ? t->data_ptr<T>() : nullptr;
+}
+void* opt_ptr(const c10::optional<Tensor>& t) {
+  return t.has_value() ? t->data_ptr() : nullptr;
+}
+
+void check_probe(const c10::optional<Tensor>& prev,
+                 const c10::optional<Tensor>& sumsq,
+                 const c10::optional<Tensor>& out) {
+  TORCH_CHECK(prev.has_value() == sumsq.has_value()
+                  && prev.has_value() == out.has_value(),
+              "probe tensors must be passed together");
 }
 
 Tensor empty_cl_bf16(int64_t n, int64_t c, int64_t h, int64_t w,
@@ -996,27 +847,17 @@ void adam_step(Tensor master, Tensor grad, Tensor m, Tensor v,
                c10::optional<Tensor> probe_sumsq,
                c10::optional<Tensor> probe_out) {
   check_f32(master, "master");
-  TORCH_CHECK(probe_prev.has_value() == probe_sumsq.has_value()
-                  && probe_prev.has_value() == probe_out.has_value(),
-              "probe tensors must be passed together");
+  check_probe(probe_prev, probe_sumsq, probe_out);
   launch_adam_step(master.data_ptr<float>(), grad.data_ptr<float>(),
                    m.data_ptr<float>(), v.data_ptr<float>(),
-                   shadow.has_value() ? shadow->data_ptr() : nullptr,
-                   step_t.data_ptr<float>(), master.numel(), (float)lr,
-                   (float)b1, (float)b2, (float)eps, (float)wd,
-                   zero_grad ? 1 : 0,
-                   extra_zero.has_value() ? extra_zero->data_ptr<float>()
-                                          : nullptr,
+                   opt_ptr(shadow), step_t.data_ptr<float>(),
+                   master.numel(), (float)lr, (float)b1, (float)b2,
+                   (float)eps, (float)wd, zero_grad ? 1 : 0,
+                   opt_ptr<float>(extra_zero),
                    extra_zero.has_value() ? extra_zero->numel() : 0,
-                   grad_bf16.has_value() ? grad_bf16->data_ptr() : nullptr,
-                   (float)grad_scale,
-                   probe_prev.has_value() ? probe_prev->data_ptr<float>()
-                                          : nullptr,
-                   probe_sumsq.has_value() ? probe_sumsq->data_ptr<float>()
-                                           : nullptr,
-                   probe_out.has_value() ? probe_out->data_ptr<float>()
-                                         : nullptr,
-                   cur_stream());
+                   opt_ptr(grad_bf16), (float)grad_scale,
+                   opt_ptr<float>(probe_prev), opt_ptr<float>(probe_sumsq),
+                   opt_ptr<float>(probe_out), cur_stream());
 }
 
 void sgd_step(Tensor master, Tensor grad, c10::optional<Tensor> mom,
@@ -1026,23 +867,13 @@ void sgd_step(Tensor master, Tensor grad, c10::optional<Tensor> mom,
               c10::optional<Tensor> probe_sumsq,
               c10::optional<Tensor> probe_out) {
   check_f32(master, "master");
-  TORCH_CHECK(probe_prev.has_value() == probe_sumsq.has_value()
-                  && probe_prev.has_value() == probe_out.has_value(),
-              "probe tensors must be passed together");
+  check_probe(probe_prev, probe_sumsq, probe_out);
   launch_sgd_step(master.data_ptr<float>(), grad.data_ptr<float>(),
-                  mom.has_value() ? mom->data_ptr<float>() : nullptr,
-                  shadow.has_value() ? shadow->data_ptr() : nullptr,
-                  master.numel(), (float)lr, (float)mu, (float)wd,
-                  zero_grad ? 1 : 0,
-                  grad_bf16.has_value() ? grad_bf16->data_ptr() : nullptr,
-                  (float)grad_scale,
-                  probe_prev.has_value() ? probe_prev->data_ptr<float>()
-                                         : nullptr,
-                  probe_sumsq.has_value() ? probe_sumsq->data_ptr<float>()
-                                          : nullptr,
-                  probe_out.has_value() ? probe_out->data_ptr<float>()
-                                        : nullptr,
-                  cur_stream());
+                  opt_ptr<float>(mom), opt_ptr(shadow), master.numel(),
+                  (float)lr, (float)mu, (float)wd, zero_grad ? 1 : 0,
+                  opt_ptr(grad_bf16), (float)grad_scale,
+                  opt_ptr<float>(probe_prev), opt_ptr<float>(probe_sumsq),
+                  opt_ptr<float>(probe_out), cur_stream());
 }
 
 // Scheduled / extended forms (adam_step / sgd_step above are untouched and
@@ -1082,9 +913,7 @@ void adam_step_sched(Tensor master, Tensor grad, Tensor m, Tensor v,
                      c10::optional<Tensor> probe_sumsq,
                      c10::optional<Tensor> probe_out) {
   check_f32(master, "master");
-  TORCH_CHECK(probe_prev.has_value() == probe_sumsq.has_value()
-                  && probe_prev.has_value() == probe_out.has_value(),
-              "probe tensors must be passed together");
+  check_probe(probe_prev, probe_sumsq, probe_out);
   TORCH_CHECK(grad.numel() == master.numel() && m.numel() == master.numel()
                   && v.numel() == master.numel(),
               "grad / m / v must match master's size");
@@ -1094,20 +923,13 @@ void adam_step_sched(Tensor master, Tensor grad, Tensor m, Tensor v,
   float* st = sched_scalar(step_t, master, "step_t");
   launch_adam_step_ex(master.data_ptr<float>(), grad.data_ptr<float>(),
                       m.data_ptr<float>(), v.data_ptr<float>(),
-                      shadow.has_value() ? shadow->data_ptr() : nullptr, st,
-                      master.numel(), (float)lr, (float)b1, (float)b2,
-                      (float)eps, (float)wd, zero_grad ? 1 : 0,
-                      extra_zero.has_value() ? extra_zero->data_ptr<float>()
-                                             : nullptr,
+                      opt_ptr(shadow), st, master.numel(), (float)lr,
+                      (float)b1, (float)b2, (float)eps, (float)wd,
+                      zero_grad ? 1 : 0, opt_ptr<float>(extra_zero),
                       extra_zero.has_value() ? extra_zero->numel() : 0,
-                      grad_bf16.has_value() ? grad_bf16->data_ptr() : nullptr,
-                      (float)grad_scale,
-                      probe_prev.has_value() ? probe_prev->data_ptr<float>()
-                                             : nullptr,
-                      probe_sumsq.has_value() ? probe_sumsq->data_ptr<float>()
-                                              : nullptr,
-                      probe_out.has_value() ? probe_out->data_ptr<float>()
-                                            : nullptr,
+                      opt_ptr(grad_bf16), (float)grad_scale,
+                      opt_ptr<float>(probe_prev),
+                      opt_ptr<float>(probe_sumsq), opt_ptr<float>(probe_out),
                       table, T, out, decoupled ? 1 : 0, cur_stream());
 }
 
@@ -1122,9 +944,7 @@ void sgd_step_sched(Tensor master, Tensor grad, c10::optional<Tensor> mom,
                     c10::optional<Tensor> probe_sumsq,
                     c10::optional<Tensor> probe_out) {
   check_f32(master, "master");
-  TORCH_CHECK(probe_prev.has_value() == probe_sumsq.has_value()
-                  && probe_prev.has_value() == probe_out.has_value(),
-              "probe tensors must be passed together");
+  check_probe(probe_prev, probe_sumsq, probe_out);
   TORCH_CHECK(grad.numel() == master.numel()
                   && (!mom.has_value() || mom->numel() == master.numel()),
               "grad / mom must match master's size");
@@ -1137,19 +957,12 @@ void sgd_step_sched(Tensor master, Tensor grad, c10::optional<Tensor> mom,
   float* out = sched_scalar(lr_out, master, "lr_out");
   float* st = sched_scalar(step_t, master, "step_t");
   launch_sgd_step_ex(master.data_ptr<float>(), grad.data_ptr<float>(),
-                     mom.has_value() ? mom->data_ptr<float>() : nullptr,
-                     shadow.has_value() ? shadow->data_ptr() : nullptr,
-                     master.numel(), (float)lr, (float)mu, (float)wd,
-                     zero_grad ? 1 : 0,
-                     grad_bf16.has_value() ? grad_bf16->data_ptr() : nullptr,
-                     (float)grad_scale,
-                     probe_prev.has_value() ? probe_prev->data_ptr<float>()
-                                            : nullptr,
-                     probe_sumsq.has_value() ? probe_sumsq->data_ptr<float>()
-                                             : nullptr,
-                     probe_out.has_value() ? probe_out->data_ptr<float>()
-                                           : nullptr,
-                     st, table, T, out, nesterov ? 1 : 0, cur_stream());
+                     opt_ptr<float>(mom), opt_ptr(shadow), master.numel(),
+                     (float)lr, (float)mu, (float)wd, zero_grad ? 1 : 0,
+                     opt_ptr(grad_bf16), (float)grad_scale,
+                     opt_ptr<float>(probe_prev), opt_ptr<float>(probe_sumsq),
+                     opt_ptr<float>(probe_out), st, table, T, out,
+                     nesterov ? 1 : 0, cur_stream());
 }
 
 void permute_krsc_rsck(Tensor src, Tensor dst, Tensor meta,
@@ -1194,7 +1007,7 @@ int64_t bn_fwd_pair_bench(Tensor ws, c10::optional<Tensor> res, Tensor y,
   TORCH_CHECK(ws.numel() >= nsplit * M * C && y.numel() >= M * C &&
                   convout.numel() >= M * C && stats.numel() >= 2 * C,
               "bn_fwd_pair_bench: buffers smaller than nsplit*M*C");
-  const void* rp = res.has_value() ? res->data_ptr() : nullptr;
+  const void* rp = opt_ptr(res);
   auto st = cur_stream();
   if (lpr == 0) {
     launch_stats_reduce(ws.data_ptr<float>(), stats.data_ptr<float>(), M,
@@ -1228,7 +1041,7 @@ int64_t bn_bwd_pair_bench(Tensor dy, Tensor y, Tensor x, Tensor mean,
                   x.numel() >= M * C && dconv.numel() >= M * C &&
                   sdz.numel() >= C && sdzx.numel() >= C,
               "bn_bwd_pair_bench: buffers smaller than M*C");
-  void* drp = dres.has_value() ? dres->data_ptr() : nullptr;
+  void* drp = opt_ptr(dres);
   auto st = cur_stream();
   if (lpr == 0) {
     launch_bnact_bwd_reduce(dy.data_ptr(), y.data_ptr(), x.data_ptr(),

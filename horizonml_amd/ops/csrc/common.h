@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include "launch.h"  // ConvP, MagicP, task tables, launcher declarations
+
 #define WAVE 64
 #define DEV __device__ __forceinline__
 
@@ -32,16 +34,7 @@ DEV float wave_reduce_sum(float x) {
   return x;
 }
 
-// Fast division by a runtime constant (cutlass FastDivmod form):
-// q = (umulhi(n, m) + n) >> s for 1 < d < 2^31, 0 <= n < 2^31; d == 1 is
-// the identity.  The implicit-GEMM gathers decompose linear indices with
-// 4-5 divisions per vec8 — emulated u32 division costs ~25-40 VALU each.
-struct MagicP {
-  unsigned m[4];
-  int s[4];
-  unsigned d[4];
-};
-
+// Device side of MagicP (launch.h): q = (umulhi(n, m) + n) >> s.
 DEV unsigned fdiv(unsigned n, const MagicP& mg, int i) {
   return mg.d[i] == 1 ? n : (__umulhi(n, mg.m[i]) + n) >> mg.s[i];
 }

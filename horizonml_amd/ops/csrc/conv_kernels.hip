@@ -24,48 +24,7 @@
 // statistics (Σy, Σy²) via wave shuffle reduction + one atomicAdd per
 // 16-lane group, so a training conv+BN block is 2 kernels total
 // (north-star fused conv+BN+ReLU).
-#include <cstdlib>
-
-#include "common.h"
-
-struct ConvP {
-  int Nb, H, W, C, K;      // batch, input spatial, in/out channels
-  int Ho, Wo, R, S;        // output spatial, filter
-  int str, pad;
-  int M, Kd;               // GEMM rows, reduction size
-};
-
-// ------------------------------------------------------------- fast div ----
-static void magic_u32(unsigned d, unsigned* m, int* sh) {
-  if (d <= 1) { *m = 0; *sh = 0; return; }
-  int p = 0;
-  while ((1ull << p) < d) p++;
-  *m = (unsigned)((((unsigned long long)((1ull << p) - d) << 32) / d) + 1);
-  *sh = p;
-}
-
-// gather divisors per mode: MODE1 {Ho*Wo, Wo, S*C, C};
-// MODE2 {H*W, W, S*K, K} (index 3 also serves b_addr's /K %K)
-static MagicP make_magic(const ConvP& p, int mode) {
-  MagicP mg{};
-  unsigned d[4];
-  if (mode == 2) {
-    d[0] = (unsigned)(p.H * p.W);
-    d[1] = (unsigned)p.W;
-    d[2] = (unsigned)(p.S * p.K);
-    d[3] = (unsigned)p.K;
-  } else {
-    d[0] = (unsigned)(p.Ho * p.Wo);
-    d[1] = (unsigned)p.Wo;
-    d[2] = (unsigned)(p.S * p.C);
-    d[3] = (unsigned)p.C;
-  }
-  for (int i = 0; i < 4; i++) {
-    mg.d[i] = d[i] ? d[i] : 1;
-    magic_u32(mg.d[i], &mg.m[i], &mg.s[i]);
-  }
-  return mg;
-}
+#include "common.h"  // ConvP, MagicP and make_magic come from launch.h
 
 // ---------------------------------------------------------------- staging --
 template <int MODE>
@@ -545,25 +504,7 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(
 // (tile, z) blocks are in flight together so msplit can stay small
 // (mchunk ≈ 512 rows) and the grid still fills 256 CUs without atomics.
 // Task tables travel as kernel arguments by value — no staging buffers,
-// hipGraph-capture-safe.
-#define WG_MAX_TASKS 20
-
-struct WgradTask {
-  const bf16* X;
-  const bf16* Dz;
-  float* out;      // dW when msplit==1, else slab base [msplit][Ntot][Kd]
-  ConvP p;
-  MagicP mg;
-  int Ntot, mchunk, msplit, tx, ty;  // tile counts
-  int base;        // first block id of this task
-  int vec;
-};
-
-struct WgradBatchArgs {
-  int n;
-  WgradTask t[WG_MAX_TASKS];
-};
-
+// hipGraph-capture-safe.  WgradBatchArgs / WredBatchArgs: launch.h.
 template <int TK3, int TKO>
 __global__ __launch_bounds__(256) void k_wgrad_batched(WgradBatchArgs a) {
   int bid = blockIdx.x;
@@ -575,26 +516,15 @@ __global__ __launch_bounds__(256) void k_wgrad_batched(WgradBatchArgs a) {
   int z = local / nt, rem = local - z * nt;
   int ty = rem / t.tx, tx = rem - ty * t.tx;
   __shared__ WgradSmemT<TK3, TKO> smem;
+  const bf16* X = (const bf16*)t.X;
+  const bf16* Dz = (const bf16*)t.Dz;
   if (t.vec)
-    wgrad_tile<true, TK3, TKO>(t.X, t.Dz, t.out, t.p, t.mg, t.Ntot,
-                               t.mchunk, tx, ty, z, t.msplit > 1, smem);
+    wgrad_tile<true, TK3, TKO>(X, Dz, t.out, t.p, t.mg, t.Ntot, t.mchunk, tx,
+                               ty, z, t.msplit > 1, smem);
   else
-    wgrad_tile<false, TK3, TKO>(t.X, t.Dz, t.out, t.p, t.mg, t.Ntot,
-                                t.mchunk, tx, ty, z, t.msplit > 1, smem);
+    wgrad_tile<false, TK3, TKO>(X, Dz, t.out, t.p, t.mg, t.Ntot, t.mchunk,
+                                tx, ty, z, t.msplit > 1, smem);
 }
-
-struct WredTask {
-  const float* ws;
-  float* dW;
-  long n;
-  int msplit;
-  int base;  // first block id; each block covers 1024 floats
-};
-
-struct WredBatchArgs {
-  int n;
-  WredTask t[WG_MAX_TASKS];
-};
 
 __global__ __launch_bounds__(256) void k_wgrad_reduce_batched(
     WredBatchArgs a) {
@@ -633,16 +563,10 @@ static inline int cdiv_h(int a, int b) { return (a + b - 1) / b; }
 static inline int pick_splitk(int tiles, int Kd) {
   // tunables (read once): grid-fill target and minimum Kd that justifies
   // the split-K consumer chain
-  static int tile_min = [] {
-    const char* e = getenv("HZ_SK_TILES");
-    // r02 re-sweep: 256 splits the layer3/4-class long-K forwards too:
-    // r50@224 10.01 -> 9.05 ms same-box, CIFAR bs=1024 +3%, bs=64 flat
-    return e ? atoi(e) : 256;
-  }();
-  static int kd_min = [] {
-    const char* e = getenv("HZ_SK_KD");
-    return e ? atoi(e) : 1024;
-  }();
+  // r02 re-sweep: 256 splits the layer3/4-class long-K forwards too:
+  // r50@224 10.01 -> 9.05 ms same-box, CIFAR bs=1024 +3%, bs=64 flat
+  static const int tile_min = (int)env_long("HZ_SK_TILES", 256);
+  static const int kd_min = (int)env_long("HZ_SK_KD", 1024);
   if (tiles >= tile_min || Kd < kd_min) return 1;
   int sk = cdiv_h(256, tiles);
   int maxsk = cdiv_h(Kd, 32);
@@ -661,17 +585,11 @@ static inline int pick_tile_dgrad(int M, int N);
 // latency tile.  The split path pays the f32 workspace + consumer pass,
 // so this only makes sense for long-K shapes (kd floor re-used).
 static int sk_fill(int dgrad) {
-  static int vf = [] {
-    const char* e = getenv("HZ_SK_FILL");
-    return e ? atoi(e) : 0;
-  }();
-  static int vd = [] {
-    const char* e = getenv("HZ_SK_FILL_DG");
-    // swept on r50@224 bs=32 (same box): 8.536 -> 8.485 ms; the fwd
-    // variant (HZ_SK_FILL) measured flat and stays off — its split
-    // drags the stats pass + slab re-reads
-    return e ? atoi(e) : 256;
-  }();
+  static const int vf = (int)env_long("HZ_SK_FILL", 0);
+  // swept on r50@224 bs=32 (same box): 8.536 -> 8.485 ms; the fwd
+  // variant (HZ_SK_FILL) measured flat and stays off — its split
+  // drags the stats pass + slab re-reads
+  static const int vd = (int)env_long("HZ_SK_FILL_DG", 256);
   return dgrad ? vd : vf;
 }
 
@@ -699,14 +617,9 @@ extern "C" int conv_dgrad_splitk(ConvP p) {
   // threshold: its split path costs only the cast pass (often fused with
   // the upstream conv's BN reduce), so splitting pays at smaller Kd than
   // the forward's split (which drags a stats pass + slab re-reads).
-  static int kd_min_dg = [] {
-    const char* e = getenv("HZ_SK_KD_DG");
-    return e ? atoi(e) : 512;
-  }();
-  static int tile_min_dg = [] {
-    const char* e = getenv("HZ_SK_TILES_DG");
-    return e ? atoi(e) : 256;  // swept: r50@224 9.05 -> 8.89 ms; CIFAR flat
-  }();
+  static const int kd_min_dg = (int)env_long("HZ_SK_KD_DG", 512);
+  // swept: r50@224 9.05 -> 8.89 ms; CIFAR flat
+  static const int tile_min_dg = (int)env_long("HZ_SK_TILES_DG", 256);
   int tiles = cdiv_h(p.C, 64) * cdiv_h(p.Nb * p.H * p.W, 64);
   int Kd = p.R * p.S * p.K;
   if (tiles >= tile_min_dg || Kd < kd_min_dg) {
@@ -867,10 +780,7 @@ static inline bool stem_eligible(const ConvP& p) {
   // staging (64x232 padded image re-built 3.5k times) eats the gather
   // savings.  Kept as an opt-in experiment + measured negative
   // (docs/STATUS.md); default OFF.
-  static int on = [] {
-    const char* e = getenv("HZ_STEM_DIRECT");
-    return e ? atoi(e) : 0;
-  }();
+  static const int on = (int)env_long("HZ_STEM_DIRECT", 0);
   return on && p.C == 3 && p.R == 7 && p.S == 7 && p.str == 2 &&
          p.pad == 3 && p.K <= 64 && p.Wo <= 128;
 }
@@ -915,44 +825,21 @@ static inline int pick_tile_env(int M, int N, int fill, int m_min,
 // dgrad has its own thresholds: no stats epilogue and an RSCK B-gather,
 // so the fwd-measured floors need not match (HZ_TILE_*_DG)
 static inline int pick_tile_dgrad(int M, int N) {
-  static int fill = [] {
-    const char* e = getenv("HZ_TILE_FILL_DG");
-    return e ? atoi(e) : 192;
-  }();
-  static int m_min = [] {
-    const char* e = getenv("HZ_TILE_M_MIN_DG");
-    return e ? atoi(e) : 16384;
-  }();
-  static int m256 = [] {
-    const char* e = getenv("HZ_TILE_M256_DG");
-    return e ? atoi(e) : 65536;
-  }();
+  static const int fill = (int)env_long("HZ_TILE_FILL_DG", 192);
+  static const int m_min = (int)env_long("HZ_TILE_M_MIN_DG", 16384);
+  static const int m256 = (int)env_long("HZ_TILE_M256_DG", 65536);
   return pick_tile_env(M, N, fill, m_min, m256);
 }
 
 static inline int pick_tile(int M, int N) {
-  static int fill = [] {
-    const char* e = getenv("HZ_TILE_FILL");
-    return e ? atoi(e) : 192;
-  }();
-  // measured (gpurun conv sweep, r50@224 bs=32): the 128-row tiles win
+  static const int fill = (int)env_long("HZ_TILE_FILL", 192);
+  // measured (conv sweep, r50@224 bs=32): the 128-row tiles win
   // from M≈25k up (+30-60% fwd) but lose ~20% at M≈6k even when the
   // grid-fill bound is met — keep a hard M floor
-  static int m_min = [] {
-    const char* e = getenv("HZ_TILE_M_MIN");
-    return e ? atoi(e) : 16384;
-  }();
-  static int m_min256 = [] {
-    const char* e = getenv("HZ_TILE_M256");
-    return e ? atoi(e) : 65536;
-  }();
-  if (M < m_min) return 0;
-  if (M >= m_min256 && N < 128
-      && (long)cdiv_h(M, 256) * cdiv_h(N, 64) >= fill)
-    return 3;  // 256x64: very-large-M thin-N shapes (stem/layer1 @224)
-  if (N >= 128 && (long)cdiv_h(M, 128) * cdiv_h(N, 128) >= fill) return 2;
-  if ((long)cdiv_h(M, 128) * cdiv_h(N, 64) >= fill) return 1;
-  return 0;
+  static const int m_min = (int)env_long("HZ_TILE_M_MIN", 16384);
+  // 256x64 (tile 3): very-large-M thin-N shapes (stem/layer1 @224)
+  static const int m_min256 = (int)env_long("HZ_TILE_M256", 65536);
+  return pick_tile_env(M, N, fill, m_min, m_min256);
 }
 
 // Non-split forward (bf16 out + fused stats).
@@ -1074,10 +961,10 @@ extern "C" void launch_gemm_bf16(const void* a, const void* b, void* c, int M,
 // tile class per task batch: tx/ty counted in (tk3, tko)-wide tiles by
 // the caller.  128-wide k3 halves Dz re-reads; 128-wide ko halves X
 // re-reads; both double the MFMA per staging write.
-extern "C" void launch_wgrad_batched_t(const void* args, int blocks,
+extern "C" void launch_wgrad_batched_t(const WgradBatchArgs* args, int blocks,
                                        int tk3, int tko, hipStream_t st) {
   if (blocks <= 0) return;
-  const WgradBatchArgs& a = *(const WgradBatchArgs*)args;
+  const WgradBatchArgs& a = *args;
   if (tk3 == 128 && tko == 128)
     k_wgrad_batched<128, 128><<<blocks, 256, 0, st>>>(a);
   else if (tk3 == 128)
@@ -1088,11 +975,9 @@ extern "C" void launch_wgrad_batched_t(const void* args, int blocks,
     k_wgrad_batched<64, 64><<<blocks, 256, 0, st>>>(a);
 }
 
-extern "C" void launch_wgrad_reduce_batched(const void* args, int blocks,
-                                            hipStream_t st) {
-  if (blocks > 0)
-    k_wgrad_reduce_batched<<<blocks, 256, 0, st>>>(
-        *(const WredBatchArgs*)args);
+extern "C" void launch_wgrad_reduce_batched(const WredBatchArgs* args,
+                                            int blocks, hipStream_t st) {
+  if (blocks > 0) k_wgrad_reduce_batched<<<blocks, 256, 0, st>>>(*args);
 }
 
 extern "C" int wgrad_msplit(ConvP p) {

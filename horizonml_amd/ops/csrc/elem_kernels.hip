@@ -2,7 +2,6 @@
 // All activation tensors are bf16 NHWC (flattened [M][C], channels innermost,
 // coalesced along C); statistics and parameters are f32.
 #include <cstdio>
-#include <cstdlib>
 
 #include "common.h"
 
@@ -2109,165 +2108,85 @@ __global__ void k_gdiv_finalize(float* __restrict__ sumsq,
 }
 
 // ------------------------------------------------------------- launchers --
-static inline int gsz_cap() {
-  static int cap = [] {
-    const char* e = getenv("HZ_GSZ_CAP");
-    return e ? atoi(e) : 4096;
-  }();
-  return cap;
-}
-
 static inline int gsz(long total, int block = 256, int cap = 0) {
-  if (cap == 0) cap = gsz_cap();
+  static const int dflt_cap = (int)env_long("HZ_GSZ_CAP", 4096);
+  if (cap == 0) cap = dflt_cap;
   long g = (total + block - 1) / block;
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return (int)g;
 }
 
-extern "C" {
-
 static int g_det_kernels = 0;
-void set_kernels_deterministic(int on) { g_det_kernels = on; }
 
-void launch_stats_bf16_det(const void* x, float* stats, long M, int C,
-                           hipStream_t st) {
-  k_stats_bf16_det<<<(C + 63) / 64, 256, 0, st>>>((const bf16*)x, stats, M,
-                                                  C);
-}
+// Grid of the row-split kernels: blockIdx.x walks `xext` channel blocks or
+// slabs, blockIdx.y walks msplit chunks of mchunk rows.  msplit fills a
+// `budget` of blocks, capped at `cap` (0 = no cap) and at one split per
+// `rows_min` rows (0 = no floor); deterministic mode (where `det_single`)
+// keeps one split, i.e. a fixed cross-block reduction order.
+struct MSplitGrid {
+  dim3 grid;
+  long mchunk;
+};
 
-static int bn_v8_iters();
-static int bn_v8_cslab(int C);
-
-// grid sizing for the c-blocked apply kernels: <=512-ch slabs x
-// m-chunks.  Unlike the reduce kernels (whose per-block LDS epilogue +
-// atomics reward long m-loops, bn_v8_iters), apply has no epilogue and
-// its f32 split-K slab-sum is LATENCY-bound — one m-row per thread,
-// i.e. maximum thread parallelism, measured 4x faster at the small
-// CIFAR shapes (30.2 -> ~7 us); the 768-block cap keeps big-M shapes
-// at the same fill as before.
-static dim3 bn_apply_grid(long M, int C, long* mchunk_out, int* cslab_out) {
-  int cslab = bn_v8_cslab(C), nslab = C / cslab;
-  int lpr = cslab >> 3, mstep = 256 / lpr;
-  int msplit = (int)min((long)max(1, 768 / nslab),
-                        max((long)1, (M + mstep - 1) / mstep));
+static MSplitGrid msplit_grid(long M, int xext, int budget, long cap,
+                              long rows_min, bool det_single) {
+  long msplit = max(1, budget / xext);
+  if (cap > 0) msplit = min(msplit, cap);
+  if (rows_min > 0)
+    msplit = min(msplit, max((long)1, (M + rows_min - 1) / rows_min));
+  if (det_single && g_det_kernels) msplit = 1;
   long mchunk = (M + msplit - 1) / msplit;
-  msplit = (int)((M + mchunk - 1) / mchunk);
-  *mchunk_out = mchunk;
-  *cslab_out = cslab;
-  return dim3(nslab, msplit);
+  msplit = (M + mchunk - 1) / mchunk;
+  return {dim3(xext, (unsigned)msplit), mchunk};
 }
 
-void launch_bn_apply(const void* x, const void* res, void* y,
-                     const float* stats, const float* gamma,
-                     const float* beta, float* rmean, float* rvar,
-                     float* smean, float* sinvstd, long M, int C,
-                     float momentum, float eps, int training, int act,
-                     hipStream_t st) {
-  if ((C & 7) == 0 && bn_v8_cslab(C) <= 2048) {
-    // slab <= 2048 keeps lpr <= 256 (a C = 8 x large-prime extent has no
-    // viable slab divisor and would make mstep = 0) — such channel
-    // counts fall back to the flat elementwise kernel
-    long mchunk; int cslab;
-    dim3 grid = bn_apply_grid(M, C, &mchunk, &cslab);
-#define LF(AC, TR) k_bn_apply_v8<false, AC, TR><<<grid, 256, 0, st>>>( \
-    x, (const bf16*)res, (bf16*)y, nullptr, stats, gamma, beta, rmean, \
-    rvar, smean, sinvstd, M, C, momentum, eps, 1, mchunk, cslab)
-    if (training) {
-      if (act == 1) LF(1, true); else if (act == 2) LF(2, true);
-      else LF(0, true);
-    } else {
-      if (act == 1) LF(1, false); else if (act == 2) LF(2, false);
-      else LF(0, false);
-    }
-#undef LF
-    return;
+// the scalar reduce-style kernels: 64-channel columns, <= 768 blocks,
+// <= 256 splits
+static MSplitGrid scalar_reduce_grid(long M, int C, bool det_single = true) {
+  return msplit_grid(M, (C + 63) / 64, 768, 256, 0, det_single);
+}
+
+// Runtime value -> compile-time constant: f receives
+// std::integral_constant<int, MASK> for mask_mode 0..4 (anything else is 0).
+template <class F>
+static void with_mask(int mask_mode, F&& f) {
+  switch (mask_mode) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 0>{}); break;
   }
-#define LF(AC, TR) k_bn_apply<false, AC, TR><<<gsz(M * (long)C / 8 + 1), \
-    256, 0, st>>>(x, (const bf16*)res, (bf16*)y, nullptr, stats, gamma, \
-    beta, rmean, rvar, smean, sinvstd, M, C, momentum, eps, 1)
-  if (training) {
-    if (act == 1) LF(1, true); else if (act == 2) LF(2, true);
-    else LF(0, true);
-  } else {
-    if (act == 1) LF(1, false); else if (act == 2) LF(2, false);
-    else LF(0, false);
-  }
-#undef LF
 }
 
-void launch_bn_apply_f32(const float* ws, const void* res, void* y,
-                         void* convout, const float* stats,
-                         const float* gamma, const float* beta, float* rmean,
-                         float* rvar, float* smean, float* sinvstd, long M,
-                         int C, float momentum, float eps, int training,
-                         int act, int nsplit, hipStream_t st) {
-  if ((C & 7) == 0 && bn_v8_cslab(C) <= 2048) {
-    // slab <= 2048 keeps lpr <= 256 (a C = 8 x large-prime extent has no
-    // viable slab divisor and would make mstep = 0) — such channel
-    // counts fall back to the flat elementwise kernel
-    long mchunk; int cslab;
-    dim3 grid = bn_apply_grid(M, C, &mchunk, &cslab);
-#define LF(AC, TR) k_bn_apply_v8<true, AC, TR><<<grid, 256, 0, st>>>( \
-    ws, (const bf16*)res, (bf16*)y, (bf16*)convout, stats, gamma, beta, \
-    rmean, rvar, smean, sinvstd, M, C, momentum, eps, nsplit, mchunk, cslab)
-    if (training) {
-      if (act == 1) LF(1, true); else if (act == 2) LF(2, true);
-      else LF(0, true);
-    } else {
-      if (act == 1) LF(1, false); else if (act == 2) LF(2, false);
-      else LF(0, false);
-    }
-#undef LF
-    return;
-  }
-#define LF(AC, TR) k_bn_apply<true, AC, TR><<<gsz(M * (long)C / 8 + 1), \
-    256, 0, st>>>(ws, (const bf16*)res, (bf16*)y, (bf16*)convout, stats, \
-    gamma, beta, rmean, rvar, smean, sinvstd, M, C, momentum, eps, nsplit)
-  if (training) {
-    if (act == 1) LF(1, true); else if (act == 2) LF(2, true);
-    else LF(0, true);
-  } else {
-    if (act == 1) LF(1, false); else if (act == 2) LF(2, false);
-    else LF(0, false);
-  }
-#undef LF
+// act 0..2 (anything else is 0) as std::integral_constant<int, ACT>
+template <class F>
+static void with_act(int act, F&& f) {
+  if (act == 1) f(std::integral_constant<int, 1>{});
+  else if (act == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 0>{});
 }
 
-void launch_stats_reduce(const float* ws, float* stats, long M, int C,
-                         int nsplit, hipStream_t st) {
-  int cblocks = (C + 63) / 64;
-  int msplit = (int)min((long)256, max((long)1, (long)(768 / cblocks)));
-  if (g_det_kernels) msplit = 1;  // fixed cross-block reduction order
-  long mchunk = (M + msplit - 1) / msplit;
-  msplit = (int)((M + mchunk - 1) / mchunk);
-  dim3 grid(cblocks, msplit);
-  k_stats_reduce<<<grid, 256, 0, st>>>(ws, stats, M, C, mchunk, nsplit);
+// (act, training) as (integral_constant<int, ACT>, bool_constant<TRAIN>)
+template <class F>
+static void with_act_train(int act, int training, F&& f) {
+  auto go = [&](auto tr) { with_act(act, [&](auto ac) { f(ac, tr); }); };
+  if (training) go(std::true_type{});
+  else go(std::false_type{});
 }
 
-void launch_cast_f32_bf16(const float* src, void* dst, long n, int nsplit,
-                          int accum, hipStream_t st) {
-  k_cast_f32_bf16<<<gsz(n / 8 + 1), 256, 0, st>>>(src, (bf16*)dst, n,
-                                                   nsplit, accum);
-}
-
+// ---- v8 BatchNorm dispatch knobs --------------------------------------------
 static int bn_v8_enabled() {
-  static int v = [] {
-    const char* e = getenv("HZ_BN_V8");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = (int)env_long("HZ_BN_V8", 1);
   return v;
 }
 
-// v8 wins from M >= ~65k rows (isolated sweep gpurun_out/bn_v8c.txt:
-// 3.0 TB/s vs 0.7 at M=401k/C=64); below that the scalar kernel's
-// per-channel-column layout is faster — per-block setup + atomic volume
-// dominate the short v8 m-loops.
+// v8 wins from M >= ~65k rows (isolated sweep: 3.0 TB/s vs 0.7 at
+// M=401k/C=64); below that the scalar kernel's per-channel-column layout is
+// faster — per-block setup + atomic volume dominate the short v8 m-loops.
 static long bn_v8_m_min() {
-  static long v = [] {
-    const char* e = getenv("HZ_BN_V8_MMIN");
-    return e ? atol(e) : 65536L;
-  }();
+  static const long v = env_long("HZ_BN_V8_MMIN", 65536L);
   return v;
 }
 
@@ -2275,20 +2194,15 @@ static long bn_v8_m_min() {
 // blocks): more iterations -> fewer blocks -> less per-block epilogue +
 // atomic volume, at the cost of m-parallelism.
 static int bn_v8_iters() {
-  static int v = [] {
-    const char* e = getenv("HZ_BN_V8_ITERS");
-    return e ? atoi(e) : 8;  // swept: big-M flat, mid-M 1.5-2.5x faster
-  }();
+  // swept: big-M flat, mid-M 1.5-2.5x faster
+  static const int v = (int)env_long("HZ_BN_V8_ITERS", 8);
   return v;
 }
 
 // mid-M floor for the C <= 512 full-slab rule (swept: scalar kernel wins
 // below ~6k rows there).
 static long bn_v8_mid_m() {
-  static long v = [] {
-    const char* e = getenv("HZ_BN_V8_MIDM");
-    return e ? atol(e) : 6000L;
-  }();
+  static const long v = env_long("HZ_BN_V8_MIDM", 6000L);
   return v;
 }
 
@@ -2296,18 +2210,12 @@ static long bn_v8_mid_m() {
 // into <=512-channel slabs (keeps >=4 m-rows per block).  Floor swept on
 // the r50@224 leftovers (M=1568..6272, C=1024/2048).
 static int bn_v8_slab_enabled() {
-  static int v = [] {
-    const char* e = getenv("HZ_BN_V8_SLAB");
-    return e ? atoi(e) : 1;
-  }();
+  static const int v = (int)env_long("HZ_BN_V8_SLAB", 1);
   return v;
 }
 
 static long bn_v8_slab_m_min() {
-  static long v = [] {
-    const char* e = getenv("HZ_BN_V8_SLAB_MMIN");
-    return e ? atol(e) : 1024L;
-  }();
+  static const long v = env_long("HZ_BN_V8_SLAB_MMIN", 1024L);
   return v;
 }
 
@@ -2333,6 +2241,108 @@ static bool bn_v8_pick(long M, int C) {
          bn_v8_cslab(C) < C;
 }
 
+// The c-blocked apply kernels take any C % 8 == 0 whose slab is <= 2048:
+// that keeps lpr <= 256 (a C = 8 x large-prime extent has no viable slab
+// divisor and would make mstep = 0) — such channel counts fall back to the
+// flat elementwise kernel.
+static bool bn_apply_v8_ok(int C) {
+  return (C & 7) == 0 && bn_v8_cslab(C) <= 2048;
+}
+
+// v8 grids: one <=512-channel slab per block (blockIdx.x), m split across
+// blockIdx.y so that every thread has >= `iters` rows and the grid reaches
+// ~768 blocks on big-M shapes (matching the scalar kernels' fill).
+static MSplitGrid bn_v8_grid(long M, int C, int iters, bool det_single,
+                             int* cslab_out) {
+  int cslab = bn_v8_cslab(C), nslab = C / cslab;
+  int lpr = cslab >> 3, mstep = 256 / lpr;
+  *cslab_out = cslab;
+  return msplit_grid(M, nslab, 768, 0, (long)mstep * iters, det_single);
+}
+
+// the reduce kernels' per-block LDS epilogue + atomics reward long m-loops
+static MSplitGrid bn_v8_reduce_grid(long M, int C, int* cslab_out) {
+  return bn_v8_grid(M, C, bn_v8_iters(), true, cslab_out);
+}
+
+// apply has no epilogue and its f32 split-K slab-sum is LATENCY-bound —
+// one m-row per thread, i.e. maximum thread parallelism, measured 4x
+// faster at the small CIFAR shapes (30.2 -> ~7 us); the 768-block cap
+// keeps big-M shapes at the same fill as before.
+static MSplitGrid bn_apply_grid(long M, int C, int* cslab_out) {
+  return bn_v8_grid(M, C, 1, false, cslab_out);
+}
+
+template <bool F32SRC>
+static void bn_apply_any(const void* x, const void* res, void* y,
+                         void* convout, const float* stats,
+                         const float* gamma, const float* beta, float* rmean,
+                         float* rvar, float* smean, float* sinvstd, long M,
+                         int C, float momentum, float eps, int training,
+                         int act, int nsplit, hipStream_t st) {
+  if (bn_apply_v8_ok(C)) {
+    int cslab;
+    MSplitGrid g = bn_apply_grid(M, C, &cslab);
+    with_act_train(act, training, [&](auto ac, auto tr) {
+      k_bn_apply_v8<F32SRC, ac.value, tr.value><<<g.grid, 256, 0, st>>>(
+          x, (const bf16*)res, (bf16*)y, (bf16*)convout, stats, gamma, beta,
+          rmean, rvar, smean, sinvstd, M, C, momentum, eps, nsplit, g.mchunk,
+          cslab);
+    });
+    return;
+  }
+  with_act_train(act, training, [&](auto ac, auto tr) {
+    k_bn_apply<F32SRC, ac.value, tr.value>
+        <<<gsz(M * (long)C / 8 + 1), 256, 0, st>>>(
+            x, (const bf16*)res, (bf16*)y, (bf16*)convout, stats, gamma,
+            beta, rmean, rvar, smean, sinvstd, M, C, momentum, eps, nsplit);
+  });
+}
+
+extern "C" {
+
+void set_kernels_deterministic(int on) { g_det_kernels = on; }
+
+void launch_stats_bf16_det(const void* x, float* stats, long M, int C,
+                           hipStream_t st) {
+  k_stats_bf16_det<<<(C + 63) / 64, 256, 0, st>>>((const bf16*)x, stats, M,
+                                                  C);
+}
+
+void launch_bn_apply(const void* x, const void* res, void* y,
+                     const float* stats, const float* gamma,
+                     const float* beta, float* rmean, float* rvar,
+                     float* smean, float* sinvstd, long M, int C,
+                     float momentum, float eps, int training, int act,
+                     hipStream_t st) {
+  bn_apply_any<false>(x, res, y, nullptr, stats, gamma, beta, rmean, rvar,
+                      smean, sinvstd, M, C, momentum, eps, training, act, 1,
+                      st);
+}
+
+void launch_bn_apply_f32(const float* ws, const void* res, void* y,
+                         void* convout, const float* stats,
+                         const float* gamma, const float* beta, float* rmean,
+                         float* rvar, float* smean, float* sinvstd, long M,
+                         int C, float momentum, float eps, int training,
+                         int act, int nsplit, hipStream_t st) {
+  bn_apply_any<true>(ws, res, y, convout, stats, gamma, beta, rmean, rvar,
+                     smean, sinvstd, M, C, momentum, eps, training, act,
+                     nsplit, st);
+}
+
+void launch_stats_reduce(const float* ws, float* stats, long M, int C,
+                         int nsplit, hipStream_t st) {
+  MSplitGrid g = scalar_reduce_grid(M, C);
+  k_stats_reduce<<<g.grid, 256, 0, st>>>(ws, stats, M, C, g.mchunk, nsplit);
+}
+
+void launch_cast_f32_bf16(const float* src, void* dst, long n, int nsplit,
+                          int accum, hipStream_t st) {
+  k_cast_f32_bf16<<<gsz(n / 8 + 1), 256, 0, st>>>(src, (bf16*)dst, n,
+                                                   nsplit, accum);
+}
+
 void launch_cast_bnact(const float* src, void* dst, long M, int C,
                        int nsplit, int accum, const void* x_up,
                        const void* y_up, const float* smean,
@@ -2340,43 +2350,21 @@ void launch_cast_bnact(const float* src, void* dst, long M, int C,
                        const float* beta, float* sum_dz, float* sum_dzx,
                        int mask_mode, hipStream_t st) {
   if (bn_v8_pick(M, C)) {
-    // vectorized: one <=512-channel slab per block (blockIdx.x), m split
-    // across blockIdx.y.  msplit sized so every thread has >=1 row and
-    // the grid reaches ~768 blocks on big-M shapes (matching the scalar
-    // kernel's fill).
-    int cslab = bn_v8_cslab(C), nslab = C / cslab;
-    int lpr = cslab >> 3, mstep = 256 / lpr;
-    int msplit = (int)min((long)max(1, 768 / nslab), max((long)1,
-        (M + (long)mstep * bn_v8_iters() - 1) /
-        ((long)mstep * bn_v8_iters())));
-    if (g_det_kernels) msplit = 1;
-    long mchunk = (M + msplit - 1) / msplit;
-    msplit = (int)((M + mchunk - 1) / mchunk);
-    dim3 grid(nslab, msplit);
-#define LC(MK) k_cast_bnact_v8<MK><<<grid, 256, 0, st>>>( \
-    src, (bf16*)dst, M, C, nsplit, accum, (const bf16*)x_up, \
-    (const bf16*)y_up, smean, sinvstd, gamma, beta, sum_dz, sum_dzx, \
-    mchunk, cslab)
-    switch (mask_mode) {
-      case 1: LC(1); break;
-      case 2: LC(2); break;
-      case 3: LC(3); break;
-      case 4: LC(4); break;
-      default: LC(0); break;
-    }
-#undef LC
+    int cslab;
+    MSplitGrid g = bn_v8_reduce_grid(M, C, &cslab);
+    with_mask(mask_mode, [&](auto mk) {
+      k_cast_bnact_v8<mk.value><<<g.grid, 256, 0, st>>>(
+          src, (bf16*)dst, M, C, nsplit, accum, (const bf16*)x_up,
+          (const bf16*)y_up, smean, sinvstd, gamma, beta, sum_dz, sum_dzx,
+          g.mchunk, cslab);
+    });
     return;
   }
-  int cblocks = (C + 63) / 64;
-  int msplit = (int)min((long)256, max((long)1, (long)(768 / cblocks)));
-  if (g_det_kernels) msplit = 1;
-  long mchunk = (M + msplit - 1) / msplit;
-  msplit = (int)((M + mchunk - 1) / mchunk);
-  dim3 grid(cblocks, msplit);
-  k_cast_bnact<<<grid, 256, 0, st>>>(src, (bf16*)dst, M, C, nsplit, accum,
-                                     (const bf16*)x_up, (const bf16*)y_up,
-                                     smean, sinvstd, gamma, beta, sum_dz,
-                                     sum_dzx, mask_mode, mchunk);
+  MSplitGrid g = scalar_reduce_grid(M, C);
+  k_cast_bnact<<<g.grid, 256, 0, st>>>(src, (bf16*)dst, M, C, nsplit, accum,
+                                       (const bf16*)x_up, (const bf16*)y_up,
+                                       smean, sinvstd, gamma, beta, sum_dz,
+                                       sum_dzx, mask_mode, g.mchunk);
 }
 
 void launch_bnact_bwd_reduce(const void* dy, const void* yout, const void* x,
@@ -2386,37 +2374,19 @@ void launch_bnact_bwd_reduce(const void* dy, const void* yout, const void* x,
                              int mask_mode, hipStream_t st) {
   // sum_dz/sum_dzx must be pre-zeroed (they are accumulated atomically)
   if (bn_v8_pick(M, C)) {
-    int cslab = bn_v8_cslab(C), nslab = C / cslab;
-    int lpr = cslab >> 3, mstep = 256 / lpr;
-    int msplit = (int)min((long)max(1, 768 / nslab), max((long)1,
-        (M + (long)mstep * bn_v8_iters() - 1) /
-        ((long)mstep * bn_v8_iters())));
-    if (g_det_kernels) msplit = 1;
-    long mchunk = (M + msplit - 1) / msplit;
-    msplit = (int)((M + mchunk - 1) / mchunk);
-    dim3 grid(nslab, msplit);
-#define LB(MK) k_bnact_bwd_reduce_v8<MK><<<grid, 256, 0, st>>>( \
-    (const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, sinvstd, \
-    gamma, beta, sum_dz, sum_dzx, M, C, mchunk, cslab)
-    switch (mask_mode) {
-      case 1: LB(1); break;
-      case 2: LB(2); break;
-      case 3: LB(3); break;
-      case 4: LB(4); break;
-      default: LB(0); break;
-    }
-#undef LB
+    int cslab;
+    MSplitGrid g = bn_v8_reduce_grid(M, C, &cslab);
+    with_mask(mask_mode, [&](auto mk) {
+      k_bnact_bwd_reduce_v8<mk.value><<<g.grid, 256, 0, st>>>(
+          (const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, sinvstd,
+          gamma, beta, sum_dz, sum_dzx, M, C, g.mchunk, cslab);
+    });
     return;
   }
-  int cblocks = (C + 63) / 64;
-  int msplit = (int)min((long)256, max((long)1, (long)(768 / cblocks)));
-  if (g_det_kernels) msplit = 1;
-  long mchunk = (M + msplit - 1) / msplit;
-  msplit = (int)((M + mchunk - 1) / mchunk);
-  dim3 grid(cblocks, msplit);
-  k_bnact_bwd_reduce<<<grid, 256, 0, st>>>(
+  MSplitGrid g = scalar_reduce_grid(M, C);
+  k_bnact_bwd_reduce<<<g.grid, 256, 0, st>>>(
       (const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, sinvstd,
-      gamma, beta, sum_dz, sum_dzx, M, C, mask_mode, mchunk);
+      gamma, beta, sum_dz, sum_dzx, M, C, mask_mode, g.mchunk);
 }
 
 void launch_bn_bwd_apply(const void* dy, const void* yout, const void* x,
@@ -2425,37 +2395,22 @@ void launch_bn_bwd_apply(const void* dy, const void* yout, const void* x,
                          const float* sum_dz, const float* sum_dzx,
                          void* dconv, void* dres, long M, int C,
                          int mask_mode, hipStream_t st) {
-  if ((C & 7) == 0 && bn_v8_cslab(C) <= 2048) {
-    // slab <= 2048 keeps lpr <= 256 (a C = 8 x large-prime extent has no
-    // viable slab divisor and would make mstep = 0) — such channel
-    // counts fall back to the flat elementwise kernel
-    long mchunk; int cslab;
-    dim3 grid = bn_apply_grid(M, C, &mchunk, &cslab);
-#define LA(MK) k_bn_bwd_apply_v8<MK><<<grid, 256, 0, st>>>( \
-    (const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, sinvstd, \
-    gamma, beta, sum_dz, sum_dzx, (bf16*)dconv, (bf16*)dres, M, C, \
-    mchunk, cslab)
-    switch (mask_mode) {
-      case 1: LA(1); break;
-      case 2: LA(2); break;
-      case 3: LA(3); break;
-      case 4: LA(4); break;
-      default: LA(0); break;
-    }
-#undef LA
+  if (bn_apply_v8_ok(C)) {
+    int cslab;
+    MSplitGrid g = bn_apply_grid(M, C, &cslab);
+    with_mask(mask_mode, [&](auto mk) {
+      k_bn_bwd_apply_v8<mk.value><<<g.grid, 256, 0, st>>>(
+          (const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, sinvstd,
+          gamma, beta, sum_dz, sum_dzx, (bf16*)dconv, (bf16*)dres, M, C,
+          g.mchunk, cslab);
+    });
     return;
   }
-#define LA(MK) k_bn_bwd_apply<MK><<<gsz(M * (long)C / 8 + 1), 256, 0, \
-    st>>>((const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, \
-    sinvstd, gamma, beta, sum_dz, sum_dzx, (bf16*)dconv, (bf16*)dres, M, C)
-  switch (mask_mode) {
-    case 1: LA(1); break;
-    case 2: LA(2); break;
-    case 3: LA(3); break;
-    case 4: LA(4); break;
-    default: LA(0); break;
-  }
-#undef LA
+  with_mask(mask_mode, [&](auto mk) {
+    k_bn_bwd_apply<mk.value><<<gsz(M * (long)C / 8 + 1), 256, 0, st>>>(
+        (const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, sinvstd,
+        gamma, beta, sum_dz, sum_dzx, (bf16*)dconv, (bf16*)dres, M, C);
+  });
 }
 
 // ---- channel-owner BN dispatch ---------------------------------------------
@@ -2465,10 +2420,7 @@ void launch_bn_bwd_apply(const void* dy, const void* yout, const void* x,
 // HZ_BN_OWNER_BWD_MMAX) and lanes-per-row (HZ_BN_OWNER_FWD_LPR /
 // HZ_BN_OWNER_BWD_LPR; wider = full cache lines per row, narrower = more
 // workgroups) come from scripts/gpu_bn_owner_sweep.py — docs/TUNING.md.
-static int g_bn_owner = [] {
-  const char* e = getenv("HZ_BN_OWNER");
-  return e ? atoi(e) : 1;
-}();
+static int g_bn_owner = (int)env_long("HZ_BN_OWNER", 1);  // read at load
 static long g_owner_fwd_launches = 0, g_owner_bwd_launches = 0;
 
 void set_kernels_bn_owner(int on) { g_bn_owner = on; }
@@ -2476,11 +2428,6 @@ int kernels_bn_owner() { return g_bn_owner; }
 void bn_owner_launch_counts(long* fwd, long* bwd) {
   *fwd = g_owner_fwd_launches;
   *bwd = g_owner_bwd_launches;
-}
-
-static long env_long(const char* name, long dflt) {
-  const char* e = getenv(name);
-  return e ? atol(e) : dflt;
 }
 
 // LDS image budget of the forward kernel (static LDS + this stays inside
@@ -2502,8 +2449,8 @@ int bn_owner_fwd_pick(long M, int C, int lpr_req) {
   // swept: wins at M <= 512 (layer3/4 of the flagship), ties the pair at
   // M = 1024 where 16 workgroups stream 4 MB of slabs; 2 lanes per row
   // won at every winning shape
-  static long mmax = env_long("HZ_BN_OWNER_FWD_MMAX", 512);
-  static int want = (int)env_long("HZ_BN_OWNER_FWD_LPR", 2);
+  static const long mmax = env_long("HZ_BN_OWNER_FWD_MMAX", 512);
+  static const int want = (int)env_long("HZ_BN_OWNER_FWD_LPR", 2);
   if (!g_bn_owner || g_det_kernels || (C & 7) != 0 || M < 1) return 0;
   if (lpr_req <= 0 && M > mmax) return 0;
   int lpr = owner_lpr(C, lpr_req > 0 ? lpr_req : want);
@@ -2517,14 +2464,14 @@ int bn_owner_bwd_pick(long M, int C, int lpr_req) {
   // workgroups reading 8 bytes of every 128-byte row).  Lanes per row
   // (0 = auto): narrow rows at large M for more workgroups, full lines at
   // small M where C/32 workgroups are still plenty.
-  static long mmax = env_long("HZ_BN_OWNER_BWD_MMAX", 1024);
-  static int want = (int)env_long("HZ_BN_OWNER_BWD_LPR", 0);
+  static const long mmax = env_long("HZ_BN_OWNER_BWD_MMAX", 1024);
+  static const int want = (int)env_long("HZ_BN_OWNER_BWD_LPR", 0);
   if (!g_bn_owner || g_det_kernels || (C & 7) != 0 || M < 1) return 0;
   if (M > (lpr_req > 0 ? (long)1 << 24 : mmax)) return 0;
   // swept: M*C = 256 Ki still wins (M=1024/C=256 8.3 vs 9.1 us, M=512/
   // C=512 6.4 vs 7.0), M=1024/C=512 loses 2x (15.4 vs 7.7 us: the pair
   // fills the chip there) and cost layer4 at batch 1024 0.6% of its step
-  static long emax = env_long("HZ_BN_OWNER_BWD_EMAX", 262144);
+  static const long emax = env_long("HZ_BN_OWNER_BWD_EMAX", 262144);
   if (lpr_req <= 0 && M * C > emax) return 0;
   int w = lpr_req > 0 ? lpr_req : want;
   if (w <= 0) w = (int)max((long)2, min((long)8, 1024 / M));
@@ -2542,11 +2489,11 @@ void launch_bn_fwd_owner(const float* ws, const void* res, void* y,
   if (M < rl) zg = (int)max((long)1, min((long)nsplit, rl / M));
   const size_t lds = (size_t)M * zg * lpr * 16;
   dim3 grid(C / (4 * lpr));
-#define LO(AC) k_bn_fwd_owner<AC><<<grid, 256, lds, st>>>( \
-    ws, (const bf16*)res, (bf16*)y, (bf16*)convout, gamma, beta, rmean, \
-    rvar, smean, sinvstd, (int)M, C, momentum, eps, nsplit, lpr, zg)
-  if (act == 1) LO(1); else if (act == 2) LO(2); else LO(0);
-#undef LO
+  with_act(act, [&](auto ac) {
+    k_bn_fwd_owner<ac.value><<<grid, 256, lds, st>>>(
+        ws, (const bf16*)res, (bf16*)y, (bf16*)convout, gamma, beta, rmean,
+        rvar, smean, sinvstd, (int)M, C, momentum, eps, nsplit, lpr, zg);
+  });
   g_owner_fwd_launches++;
 }
 
@@ -2557,61 +2504,42 @@ void launch_bn_bwd_owner(const void* dy, const void* yout, const void* x,
                          void* dres, long M, int C, int mask_mode, int lpr,
                          hipStream_t st) {
   dim3 grid(C / (4 * lpr));
-#define LO(MK) k_bn_bwd_owner<MK><<<grid, 256, 0, st>>>( \
-    (const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, sinvstd, \
-    gamma, beta, sum_dz, sum_dzx, (bf16*)dconv, (bf16*)dres, (int)M, C, lpr)
-  switch (mask_mode) {
-    case 1: LO(1); break;
-    case 2: LO(2); break;
-    case 3: LO(3); break;
-    case 4: LO(4); break;
-    default: LO(0); break;
-  }
-#undef LO
+  with_mask(mask_mode, [&](auto mk) {
+    k_bn_bwd_owner<mk.value><<<grid, 256, 0, st>>>(
+        (const bf16*)dy, (const bf16*)yout, (const bf16*)x, smean, sinvstd,
+        gamma, beta, sum_dz, sum_dzx, (bf16*)dconv, (bf16*)dres, (int)M, C,
+        lpr);
+  });
   g_owner_bwd_launches++;
 }
 
 void launch_dw_fwd(const void* x, const void* w, void* y, float* stats,
                    int Nb, int H, int W, int C, int Ho, int Wo, int R,
                    int S, int str, int pad, hipStream_t st) {
-  int cblocks = (C + 63) / 64;
-  long M = (long)Nb * Ho * Wo;
-  int msplit = (int)min((long)256, max((long)1, (long)(768 / cblocks)));
-  if (g_det_kernels) msplit = 1;
-  long mchunk = (M + msplit - 1) / msplit;
-  msplit = (int)((M + mchunk - 1) / mchunk);
-  dim3 grid(cblocks, msplit);
-  k_dw_fwd<<<grid, 256, 0, st>>>((const bf16*)x, (const bf16*)w, (bf16*)y,
-                                 stats, Nb, H, W, C, Ho, Wo, R, S, str, pad,
-                                 mchunk);
+  MSplitGrid g = scalar_reduce_grid((long)Nb * Ho * Wo, C);
+  k_dw_fwd<<<g.grid, 256, 0, st>>>((const bf16*)x, (const bf16*)w, (bf16*)y,
+                                   stats, Nb, H, W, C, Ho, Wo, R, S, str,
+                                   pad, g.mchunk);
 }
 
 void launch_dw_dgrad(const void* dz, const void* w, void* dx, int Nb, int H,
                      int W, int C, int Ho, int Wo, int R, int S, int str,
                      int pad, hipStream_t st) {
-  int cblocks = (C + 63) / 64;
-  long M = (long)Nb * H * W;
-  int msplit = (int)min((long)256, max((long)1, (long)(768 / cblocks)));
-  long mchunk = (M + msplit - 1) / msplit;
-  msplit = (int)((M + mchunk - 1) / mchunk);
-  dim3 grid(cblocks, msplit);
-  k_dw_dgrad<<<grid, 256, 0, st>>>((const bf16*)dz, (const bf16*)w,
-                                   (bf16*)dx, Nb, H, W, C, Ho, Wo, R, S,
-                                   str, pad, mchunk);
+  // no cross-block reduction here: deterministic mode keeps the full split
+  MSplitGrid g = scalar_reduce_grid((long)Nb * H * W, C, false);
+  k_dw_dgrad<<<g.grid, 256, 0, st>>>((const bf16*)dz, (const bf16*)w,
+                                     (bf16*)dx, Nb, H, W, C, Ho, Wo, R, S,
+                                     str, pad, g.mchunk);
 }
 
 void launch_dw_wgrad(const void* x, const void* dz, float* dw, int Nb,
                      int H, int W, int C, int Ho, int Wo, int R, int S,
                      int str, int pad, hipStream_t st) {
-  int cblocks = (C + 63) / 64;
-  long M = (long)Nb * Ho * Wo;
-  int msplit = (int)min((long)64, max((long)1, (long)(512 / cblocks)));
-  if (g_det_kernels) msplit = 1;
-  long mchunk = (M + msplit - 1) / msplit;
-  msplit = (int)((M + mchunk - 1) / mchunk);
-  dim3 grid(cblocks, msplit);
-  k_dw_wgrad<<<grid, 256, 0, st>>>((const bf16*)x, (const bf16*)dz, dw, Nb,
-                                   H, W, C, Ho, Wo, R, S, str, pad, mchunk);
+  MSplitGrid g = msplit_grid((long)Nb * Ho * Wo, (C + 63) / 64, 512, 64, 0,
+                             true);
+  k_dw_wgrad<<<g.grid, 256, 0, st>>>((const bf16*)x, (const bf16*)dz, dw, Nb,
+                                     H, W, C, Ho, Wo, R, S, str, pad,
+                                     g.mchunk);
 }
 
 void launch_maxpool_fwd(const void* x, void* y, unsigned char* idx, int Nb,
@@ -2703,12 +2631,12 @@ void launch_ce_ls_fwd_bwd(const float* logits, const long* target,
 }
 
 void launch_adam_step(float* master, float* grad, float* m, float* v,
-                      void* shadow, const float* step_t, long n, float lr,
+                      void* shadow, float* step_t, long n, float lr,
                       float b1, float b2, float eps, float wd, int zero_grad,
                       float* extra_zero, long n_extra, const void* gsrc,
                       float gscale, float* prev, float* sumsq, float* divout,
                       hipStream_t st) {
-  k_inc_step<<<1, 1, 0, st>>>((float*)step_t);
+  k_inc_step<<<1, 1, 0, st>>>(step_t);
   k_adam_step<<<gsz(n), 256, 0, st>>>(master, grad, m, v, (bf16*)shadow,
                                       step_t, n, lr, b1, b2, eps, wd,
                                       zero_grad, extra_zero, n_extra,
@@ -2734,14 +2662,14 @@ void launch_sgd_step(float* master, float* grad, float* mom, void* shadow,
 // only when it has a table to index (two-launch scheme, see
 // k_augment_normalize_u8's counter).
 void launch_adam_step_ex(float* master, float* grad, float* m, float* v,
-                         void* shadow, const float* step_t, long n, float lr,
+                         void* shadow, float* step_t, long n, float lr,
                          float b1, float b2, float eps, float wd,
                          int zero_grad, float* extra_zero, long n_extra,
                          const void* gsrc, float gscale, float* prev,
                          float* sumsq, float* divout, const float* lr_table,
                          long T, float* lr_out, int decoupled,
                          hipStream_t st) {
-  k_inc_step<<<1, 1, 0, st>>>((float*)step_t);
+  k_inc_step<<<1, 1, 0, st>>>(step_t);
 #define LA(D) k_adam_step_ex<D><<<gsz(n), 256, 0, st>>>( \
     master, grad, m, v, (bf16*)shadow, step_t, n, lr, b1, b2, eps, wd, \
     zero_grad, extra_zero, n_extra, (const bf16*)gsrc, gscale, prev, sumsq, \

@@ -8,6 +8,7 @@
     matches the installed PyTorch-ROCm.
 No hipify, no CUDA paths — the kernels are native CDNA4 HIP.
 """
+import glob
 import os
 import subprocess
 
@@ -24,15 +25,19 @@ HIPCC_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
                "-ffast-math"]
 
 
+# every translation unit (bind.cpp included) sees the csrc headers: a change
+# to any of them rebuilds all objects
+HEADERS = sorted(glob.glob(os.path.join(CSRC, "*.h")))
+
+
 def compile_hip_objects():
     objs = []
     for src in HIP_SOURCES:
         src_path = os.path.join(CSRC, src)
         obj_path = src_path.replace(".hip", ".o")
         if (not os.path.exists(obj_path)
-                or os.path.getmtime(obj_path) < os.path.getmtime(src_path)
-                or os.path.getmtime(obj_path) < os.path.getmtime(
-                    os.path.join(CSRC, "common.h"))):
+                or any(os.path.getmtime(obj_path) < os.path.getmtime(dep)
+                       for dep in [src_path] + HEADERS)):
             cmd = [os.path.join(ROCM, "bin", "hipcc"), "-c", src_path,
                    "-o", obj_path] + HIPCC_FLAGS
             print("[hipcc]", " ".join(cmd), flush=True)
@@ -46,6 +51,7 @@ def main():
     ext = CppExtension(
         "horizonml_amd.ops._C",
         [os.path.join(CSRC, "bind.cpp")],
+        depends=HEADERS,
         include_dirs=[os.path.join(ROCM, "include")],
         library_dirs=[os.path.join(ROCM, "lib")],
         libraries=["amdhip64"],
