@@ -9,8 +9,10 @@ buffers, single-kernel updates):
   hipGraph capture), ONE flat bf16 shadow the conv/linear kernels consume.
 * The fused Adam/SGD kernel updates master + emits the bf16
   shadow + zeroes the gradient buffer in a single pass over the flat range.
-* A second flat bf16 buffer holds the RSCK (dgrad) weight images, refreshed
-  by one batched permute kernel per step.
+* dgrad reads the KRSC shadow directly (transposed LDS read).  Only with
+  ``HZ_DGRAD_KRSC=0`` / ``set_dgrad_krsc(False)`` does a second flat bf16
+  buffer hold RSCK weight images, refreshed by one batched permute kernel
+  per step.
 * DP gradient sync becomes ONE bf16 all-reduce of the flat buffer.
 """
 from __future__ import annotations
@@ -69,6 +71,17 @@ class FlatParamManager:
             m._stats_buf = self.stats_arena[soff:soff + 2 * m.out_ch]
             soff += 2 * m.out_ch
 
+        # KRSC-direct dgrad (the default) reads the shadow itself: no RSCK
+        # image, no per-step permute.  ``rsck`` stays a (0-element) tensor
+        # so state snapshots and checkpoints treat both modes alike.
+        self.meta = None
+        self.max_elem = 1
+        if _ops.extension().dgrad_krsc_enabled():
+            self.rsck = torch.zeros(0, device=device, dtype=torch.bfloat16)
+            for m, _, _ in convs:
+                if hasattr(m, "_w_rsck"):  # left by an earlier manager
+                    del m._w_rsck
+            return
         rsck_total = sum(wn for _, _, wn in convs)
         self.rsck = torch.zeros(rsck_total, device=device,
                                 dtype=torch.bfloat16)
@@ -86,6 +99,8 @@ class FlatParamManager:
         self.refresh_rsck()
 
     def refresh_rsck(self):
+        """Rebuild the RSCK images from the shadow (legacy dgrad layout);
+        launches nothing when the manager keeps no image."""
         if self.meta is not None:
             _ops.extension().permute_krsc_rsck(self.shadow, self.rsck,
                                                self.meta, self.max_elem)
@@ -103,8 +118,9 @@ def _sched_buffers(schedule, dev):
 
 
 class HorizonAdam:
-    """Fused flat-buffer Adam (K9): 1 elementwise kernel + step increment +
-    batched RSCK permute per step; zero_grad folded in.
+    """Fused flat-buffer Adam (K9): 1 elementwise kernel + step increment
+    per step (+ the batched RSCK permute in the legacy dgrad layout);
+    zero_grad folded in.
 
     ``schedule`` (an ``LRSchedule``): the learning rate of update ``t`` is
     read on the device from the schedule's table, indexed by ``step_t`` — a

@@ -63,12 +63,9 @@ class ConvBNActFn(torch.autograd.Function):
             ctx.saved_tensors
         mod = ctx.mod
         need_dx = ctx.needs_input_grad[0]
-        # RSCK weight image for the dgrad implicit GEMM (B-fragment wants
-        # contiguous out-channels at fixed (r,s,c)); the engine pre-builds
-        # this per step via the batched permute kernel, else permute here.
-        w_rsck = getattr(mod, "_w_rsck", None)
-        if need_dx and (w_rsck is None or w_rsck.numel() != w_bf16.numel()):
-            w_rsck = w_bf16.permute(1, 2, 3, 0).contiguous()
+        # dgrad weight slot: None = read the KRSC weight directly (default);
+        # legacy layout = an RSCK image (see _rsck)
+        w_rsck = _rsck(mod, w_bf16) if need_dx else None
         dy = _cl(dy.to(torch.bfloat16) if dy.dtype != torch.bfloat16 else dy)
         # Direct-grad mode (FlatParamManager): kernels accumulate straight
         # into the pre-zeroed flat .grad views and we return None so autograd
@@ -79,7 +76,7 @@ class ConvBNActFn(torch.autograd.Function):
         dg_out = mod.bn_weight.grad if direct else None
         db_out = mod.bn_bias.grad if direct else None
         dx, dw, dgamma, dbeta, dres = _C().conv_bn_act_bwd(
-            dy, y, x, w_bf16, w_rsck if need_dx else w_bf16, convout, gamma,
+            dy, y, x, w_bf16, w_rsck, convout, gamma,
             beta, smean, sinvstd, mod.stride, mod.padding, mod.act, need_dx,
             ctx.has_res, dw_out, dg_out, db_out, None, None, 0, False, None,
             None)
@@ -236,6 +233,13 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor,
 
 
 def _rsck(mod, w_bf16):
+    """What goes into ``conv_bn_act_bwd``'s ``w_rsck`` slot.  KRSC-direct
+    dgrad (default): ``None`` — the kernel reads ``w_bf16`` as it lies.
+    Legacy layout (``HZ_DGRAD_KRSC=0``): the RSCK image (B-fragment rows
+    contiguous along out-channels) the flat engine pre-builds per step via
+    the batched permute kernel, else a permuted copy made here."""
+    if _C().dgrad_krsc_enabled():
+        return None
     w = getattr(mod, "_w_rsck", None)
     if w is None or w.numel() != w_bf16.numel():
         w = w_bf16.permute(1, 2, 3, 0).contiguous()

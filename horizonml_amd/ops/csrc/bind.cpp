@@ -41,6 +41,16 @@ std::vector<int64_t> bn_owner_launches() {
   return {(int64_t)f, (int64_t)b};
 }
 
+// KRSC-direct dgrad: dgrad reads the KRSC weights themselves, so no RSCK
+// image is kept or rebuilt per step.  The switch (HZ_DGRAD_KRSC, read at
+// load, default on) is what the Python side consults when it decides whether
+// to build an RSCK image and pass it in conv_bn_act_bwd's w_rsck slot; the
+// slot, not the switch, selects the kernel (dgrad_dx).  Off = the former
+// RSCK path, kept for A/B timing.
+bool g_dgrad_krsc = env_long("HZ_DGRAD_KRSC", 1) != 0;
+void set_dgrad_krsc(bool on) { g_dgrad_krsc = on; }
+bool dgrad_krsc_enabled() { return g_dgrad_krsc; }
+
 // ---- deferred (batched) wgrad ---------------------------------------------
 // The weight-gradient GEMMs are off the backward's critical chain (nothing
 // reads dW until the optimizer step), and each conv's own wgrad underfills
@@ -372,8 +382,113 @@ std::vector<Tensor> conv_bn_act_fwd(
   return {y, convout, smean, sinvstd};
 }
 
+// dx of one conv from its dz (`dconv`): the split decision, the dgrad
+// launch, the slab sum and the optional fused upstream BN-backward sums
+// (fuse_up, see conv_bn_act_bwd).  p is the FORWARD geometry of the conv.
+//
+// Weight layout: `w_rsck` absent, or the KRSC weight `w` itself, selects the
+// KRSC-direct B path; any other tensor is taken as the permuted RSCK image
+// and runs MODE 2 on it.  With dx_accum given, dgrad ACCUMULATES into it
+// (dx_total = dx + residual-path grad without a separate add kernel).
+Tensor dgrad_dx(const Tensor& dconv, const Tensor& w,
+                const c10::optional<Tensor>& w_rsck, const ConvP& p,
+                const c10::optional<Tensor>& dx_accum,
+                const c10::optional<std::vector<Tensor>>& fuse_up,
+                int up_mask_mode, hipStream_t st) {
+  const bool krsc =
+      !w_rsck.has_value() || w_rsck->data_ptr() == w.data_ptr();
+  const Tensor& wt = krsc ? w : *w_rsck;
+  TORCH_CHECK(wt.is_contiguous() && wt.scalar_type() == torch::kBFloat16,
+              krsc ? "w must be contiguous bf16"
+                   : "w_rsck must be contiguous bf16");
+  TORCH_CHECK(wt.numel() == (int64_t)p.K * p.R * p.S * p.C,
+              "dgrad weight has ", wt.numel(), " elements, expected K*R*S*C");
+  auto fopt = dconv.options().dtype(torch::kFloat32);
+  const int layout = krsc ? DGRAD_W_KRSC : DGRAD_W_RSCK;
+  int accum = dx_accum.has_value() ? 1 : 0;
+  Tensor dx = accum ? *dx_accum : empty_cl_bf16(p.Nb, p.C, p.H, p.W, dconv);
+  ConvP pd = p;
+  pd.M = p.Nb * p.H * p.W;
+  pd.Kd = p.R * p.S * p.K;
+  int splitk = conv_dgrad_splitk(p);
+  const bool fuse = fuse_up.has_value();
+  if (splitk > 1) {
+    int kchunk = ((pd.Kd + splitk - 1) / splitk + 31) / 32 * 32;
+    splitk = (pd.Kd + kchunk - 1) / kchunk;
+    Tensor wsd = at::empty({(long)splitk * pd.M * p.C}, fopt);
+    launch_conv_dgrad(dconv.data_ptr(), wt.data_ptr(), nullptr,
+                      wsd.data_ptr<float>(), splitk, pd, 0, layout, st);
+    if (fuse) {
+      auto& f = *fuse_up;
+      launch_cast_bnact(wsd.data_ptr<float>(), dx.data_ptr(), (long)pd.M,
+                        p.C, splitk, accum, f[0].data_ptr(),
+                        f[1].defined() ? f[1].data_ptr() : f[0].data_ptr(),
+                        f[2].data_ptr<float>(), f[3].data_ptr<float>(),
+                        f[4].data_ptr<float>(), f[5].data_ptr<float>(),
+                        f[6].data_ptr<float>(), f[7].data_ptr<float>(),
+                        up_mask_mode, st);
+    } else {
+      launch_cast_f32_bf16(wsd.data_ptr<float>(), dx.data_ptr(),
+                           (long)pd.M * p.C, splitk, accum, st);
+    }
+  } else {
+    launch_conv_dgrad(dconv.data_ptr(), wt.data_ptr(), dx.data_ptr(), nullptr,
+                      1, pd, accum, layout, st);
+    if (fuse) {
+      auto& f = *fuse_up;
+      launch_bnact_bwd_reduce(dx.data_ptr(), f[1].defined()
+                                  ? f[1].data_ptr() : f[0].data_ptr(),
+                              f[0].data_ptr(), f[2].data_ptr<float>(),
+                              f[3].data_ptr<float>(),
+                              f[4].data_ptr<float>(),
+                              f[5].data_ptr<float>(),
+                              f[6].data_ptr<float>(),
+                              f[7].data_ptr<float>(), (long)pd.M, p.C,
+                              up_mask_mode, st);
+    }
+  }
+  return dx;
+}
+
+// Test/debug entry, the dgrad counterpart of wgrad_only: exactly the dx
+// dispatch of conv_bn_act_bwd without the BN backward in front (whose
+// channel sums are atomic-order dependent).  dz is the conv-output gradient
+// [Nb,K,Ho,Wo], w the KRSC weight, H/W the input size.
+Tensor conv_dgrad_only(Tensor dz, Tensor w, int64_t H, int64_t W,
+                       int64_t stride, int64_t pad,
+                       c10::optional<Tensor> w_rsck,
+                       c10::optional<Tensor> dx_accum) {
+  check_cl(dz, "dz");
+  TORCH_CHECK(w.dim() == 4 && w.size(0) == dz.size(1),
+              "w must be [K,R,S,C] with K = dz channels");
+  ConvP p{};
+  p.Nb = (int)dz.size(0);
+  p.C = (int)w.size(3);
+  p.H = (int)H;
+  p.W = (int)W;
+  p.K = (int)w.size(0);
+  p.R = (int)w.size(1);
+  p.S = (int)w.size(2);
+  p.str = (int)stride;
+  p.pad = (int)pad;
+  p.Ho = (p.H + 2 * p.pad - p.R) / p.str + 1;
+  p.Wo = (p.W + 2 * p.pad - p.S) / p.str + 1;
+  p.M = p.Nb * p.Ho * p.Wo;
+  p.Kd = p.R * p.S * p.C;
+  TORCH_CHECK(dz.size(2) == p.Ho && dz.size(3) == p.Wo,
+              "dz spatial size does not match H, W, stride, pad");
+  if (dx_accum.has_value()) {
+    check_cl(*dx_accum, "dx_accum");
+    TORCH_CHECK(dx_accum->size(0) == p.Nb && dx_accum->size(1) == p.C &&
+                    dx_accum->size(2) == p.H && dx_accum->size(3) == p.W,
+                "dx_accum must be [Nb,C,H,W]");
+  }
+  return dgrad_dx(dz, w, w_rsck, p, dx_accum, c10::nullopt, 0, cur_stream());
+}
+
 std::vector<Tensor> conv_bn_act_bwd(
-    Tensor dy, Tensor y, Tensor x, Tensor w, Tensor w_rsck, Tensor convout,
+    Tensor dy, Tensor y, Tensor x, Tensor w, c10::optional<Tensor> w_rsck,
+    Tensor convout,
     Tensor gamma, Tensor beta, Tensor save_mean, Tensor save_invstd,
     int64_t stride, int64_t pad, int64_t act, bool need_dx, bool has_res,
     c10::optional<Tensor> dw_out, c10::optional<Tensor> dgamma_out,
@@ -470,56 +585,9 @@ std::vector<Tensor> conv_bn_act_bwd(
               "fuse_up requires need_dx (the fused reduce rides the dx "
               "production)");
   Tensor dx;
-  if (need_dx) {
-    TORCH_CHECK(w_rsck.is_contiguous() &&
-                    w_rsck.scalar_type() == torch::kBFloat16,
-                "w_rsck must be contiguous bf16");
-    // Fused residual-junction add: with dx_accum given, dgrad ACCUMULATES
-    // into it (dx_total = dx + residual-path grad without a separate
-    // elementwise add kernel).
-    int accum = dx_accum.has_value() ? 1 : 0;
-    dx = accum ? *dx_accum : empty_cl_bf16(p.Nb, p.C, p.H, p.W, x);
-    ConvP pd = p;
-    pd.M = p.Nb * p.H * p.W;
-    pd.Kd = R * S * K;
-    int splitk = conv_dgrad_splitk(p);
-    const bool fuse = fuse_up.has_value();
-    if (splitk > 1) {
-      int kchunk = ((pd.Kd + splitk - 1) / splitk + 31) / 32 * 32;
-      splitk = (pd.Kd + kchunk - 1) / kchunk;
-      Tensor wsd = at::empty({(long)splitk * pd.M * p.C}, fopt);
-      launch_conv_dgrad(dconv.data_ptr(), w_rsck.data_ptr(), nullptr,
-                        wsd.data_ptr<float>(), splitk, pd, 0, st);
-      if (fuse) {
-        auto& f = *fuse_up;
-        launch_cast_bnact(wsd.data_ptr<float>(), dx.data_ptr(), (long)pd.M,
-                          p.C, splitk, accum, f[0].data_ptr(),
-                          f[1].defined() ? f[1].data_ptr() : f[0].data_ptr(),
-                          f[2].data_ptr<float>(), f[3].data_ptr<float>(),
-                          f[4].data_ptr<float>(), f[5].data_ptr<float>(),
-                          f[6].data_ptr<float>(), f[7].data_ptr<float>(),
-                          (int)up_mask_mode, st);
-      } else {
-        launch_cast_f32_bf16(wsd.data_ptr<float>(), dx.data_ptr(),
-                             (long)pd.M * p.C, splitk, accum, st);
-      }
-    } else {
-      launch_conv_dgrad(dconv.data_ptr(), w_rsck.data_ptr(), dx.data_ptr(),
-                        nullptr, 1, pd, accum, st);
-      if (fuse) {
-        auto& f = *fuse_up;
-        launch_bnact_bwd_reduce(dx.data_ptr(), f[1].defined()
-                                    ? f[1].data_ptr() : f[0].data_ptr(),
-                                f[0].data_ptr(), f[2].data_ptr<float>(),
-                                f[3].data_ptr<float>(),
-                                f[4].data_ptr<float>(),
-                                f[5].data_ptr<float>(),
-                                f[6].data_ptr<float>(),
-                                f[7].data_ptr<float>(), (long)pd.M, p.C,
-                                (int)up_mask_mode, st);
-      }
-    }
-  }
+  if (need_dx)
+    dx = dgrad_dx(dconv, w, w_rsck, p, dx_accum, fuse_up, (int)up_mask_mode,
+                  st);
   // dgamma = Σ dz·xhat, dbeta = Σ dz
   return {dx, dw, sum_dzx, sum_dz, dres};
 }
@@ -1174,4 +1242,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flush_wgrad", &flush_wgrad);
   m.def("flush_wgrad_range", &flush_wgrad_range);
   m.def("wgrad_only", &wgrad_only);
+  m.def("conv_dgrad_only", &conv_dgrad_only);
+  m.def("set_dgrad_krsc", &set_dgrad_krsc);
+  m.def("dgrad_krsc_enabled", &dgrad_krsc_enabled);
 }

@@ -4,6 +4,8 @@
 //   MODE 0  GEMM      C[M,N]  = A[M,Kd] · B[N,Kd]^T            (bf16 in, bf16 out)
 //   MODE 1  CONV_FWD  y[m,ko] = Σ_{r,s,c} x[patch] · W[ko,r,s,c]   (NHWC / KRSC)
 //   MODE 2  CONV_DGRAD dx[m,c] = Σ_{r,s,ko} dz[mapped] · Wr[r,s,c,ko] (RSCK)
+//   MODE 2 + KRSC     the same dgrad with B read from the KRSC weight
+//                     W[ko,r,s,c] itself (transposed LDS read, see below)
 //
 // Geometry: 64×64 block tile, BK=32 K-steps, 256 threads = 4 waves in 2×2,
 // each wave computes a 32×32 sub-tile as 2×2 mfma_f32_16x16x32_bf16
@@ -139,6 +141,63 @@ DEV V8 load8_b(const bf16* __restrict__ src, const ConvP& p,
   return v;
 }
 
+// ------------------------------------------- KRSC-direct dgrad B operand --
+// dgrad's B operand is B[k][n] with k = (r*S+s)*K + ko, n = c.  In the KRSC
+// weight a k row is contiguous along c, so a K-step tile (32 k rows × TN
+// columns) is staged AS IT LIES IN MEMORY into a [32][TN] LDS image and the
+// MFMA B-fragment (8 consecutive k of one column per lane) is fetched with
+// the gfx950 transposed read ds_read_b64_tr_b16 — no RSCK copy of the
+// weights is needed.  Operand values and K order equal MODE 2 on the RSCK
+// image, so the result is bitwise the same.
+//
+// Image: row pitch TN*2 bytes, the row's 32-byte chunks (16 columns) XORed
+// with a function of the row.  One transposed read serves, per 32-lane
+// half, two 4-row blocks 8 rows apart in the same 16 columns (groups g and
+// g+1: rows 8g+q and 8g+8+q).  A pitch that is a multiple of 32 B leaves
+// rows r and r+8 on the same banks, and a 16-B-odd pitch (the +8 pad of the
+// row-major image) always overlaps two of the eight rows, so the rows are
+// separated by the swizzle instead: with 128-B rows (TN=64) the row parity
+// picks the half of the 256-B bank row and bits {1,3} of the row pick the
+// chunk; with 256-B rows (TN=128) bits {0,1,3} do.  The eight rows of a
+// half then cover all 64 banks once: conflict-free by the bank rule.  The
+// swizzle moves whole 32-byte chunks, so the 16-byte staging stores and
+// the 8-byte-aligned transposed reads both stay inside one chunk, and the
+// second read of a fragment (rows +4) is the first one's address + 4 rows.
+template <int TN>
+DEV int krsc_off(int k, int n) {
+  const int f = TN == 64 ? (((k >> 1) & 1) | (((k >> 3) & 1) << 1))
+                         : ((k & 3) | (((k >> 3) & 1) << 2));
+  return k * TN + ((((n >> 4) ^ f)) << 4) + (n & 15);
+}
+
+// One vec8 along c of k row `k`: W[ko][r][s][n .. n+7], (rs, ko) from one
+// fdiv/fmod.  Rows past kend and columns past C are zero-filled.
+template <bool VEC>
+DEV V8 load8_b_krsc(const bf16* __restrict__ src, const ConvP& p,
+                    const MagicP& mg, int n, int k, int kend, int Ntot) {
+  V8 v;
+  unsigned rs = fdiv(k, mg, 3), ko = fmod(k, rs, mg, 3);
+  const bool kok = k < kend;
+  const int a = ((int)ko * p.R * p.S + (int)rs) * p.C + n;
+  if (VEC) {
+    if (kok && n < Ntot) v.u = *(const uint4*)(src + a);
+    else v.u = uint4{0, 0, 0, 0};
+  } else {
+    for (int e = 0; e < 8; e++)
+      v.e[e] = (kok && n + e < Ntot) ? src[a + e] : (bf16)0.f;
+  }
+  return v;
+}
+
+typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
+
+// ds_read_b64_tr_b16.  Needs EXEC all ones: call it from block-uniform
+// control flow only, with every lane's address inside the image.
+DEV bf16x4 lds_read_tr16(const bf16* sp) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4*)sp);
+}
+
 // ------------------------------------------------------------- main tile --
 #define LDA 40  // 32 + 8 pad; row stride 80 B
 
@@ -155,8 +214,13 @@ DEV V8 load8_b(const bf16* __restrict__ src, const ConvP& p,
 //    each wave runs 8/16 MFMAs per K-step against the same 6/8 LDS
 //    fragment reads, lifting the MFMA:issue ratio that caps the 64×64
 //    tile at ~2% of the bf16 peak on ResNet50@224 (r50_224_pmc_mfma.txt).
+//
+// KRSC (MODE 2 only): B is the KRSC weight; Bs holds the swizzled [32][TN]
+// image of krsc_off() in place of the [TN][LDA] one and the B fragments come
+// from transposed reads.  The A side, the accumulators, the K order and the
+// epilogue are shared with the RSCK form.
 template <int MODE, bool VECA, bool VECB, bool STATS, bool SPLIT,
-          int TM = 64, int TN = 64>
+          int TM = 64, int TN = 64, bool KRSC = false>
 __global__ __launch_bounds__(256) void k_conv_mfma(
     const bf16* __restrict__ A, const bf16* __restrict__ Bw,
     bf16* __restrict__ Y, float* __restrict__ ws_out,
@@ -170,8 +234,10 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
   constexpr int MI = TM / 32;   // 16-row m fragments per wave
   constexpr int NI = TN / 32;
   constexpr int WM = TM / 2, WN = TN / 2;
-  __shared__ bf16 As[2][TM * LDA];
-  __shared__ bf16 Bs[2][TN * LDA];
+  static_assert(!KRSC || MODE == 2, "KRSC is a dgrad B layout");
+  static_assert(!KRSC || TN == 64 || TN == 128, "krsc_off covers TN 64/128");
+  __shared__ __attribute__((aligned(16))) bf16 As[2][TM * LDA];
+  __shared__ __attribute__((aligned(16))) bf16 Bs[2][TN * LDA];  // ≥ 32*TN
 
   const int m0 = blockIdx.y * TM, n0 = blockIdx.x * TN;
   const int kbeg = SPLIT ? blockIdx.z * kchunk : 0;
@@ -181,6 +247,32 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
   const int lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   const int fr = lane & 15, fk = lane >> 4;
+  // KRSC staging: chunk j of a thread is vec8 (tid + 256 j) of the 32 × TN
+  // tile, TN/8 per k row — a wave loads whole contiguous rows of c
+  const int bkrow = tid / (TN / 8), bncol = (tid % (TN / 8)) * 8;
+  constexpr int BKSTEP = 256 / (TN / 8);  // k rows between a thread's chunks
+
+  // B tile k-origin `kt`, chunk j -> registers; registers -> LDS buffer b
+  auto load_b = [&](int j, int kt) -> V8 {
+    if (KRSC)
+      return load8_b_krsc<VECB>(Bw, p, mg, n0 + bncol,
+                                kt + j * BKSTEP + bkrow, kend, Ntot);
+    return load8_b<MODE, VECB>(Bw, p, mg, n0 + j * 64 + srow, kt + scol,
+                               Ntot);
+  };
+  auto store_b = [&](int b, int j, const V8& v) {
+    if (KRSC)
+      *(V8*)&Bs[b][krsc_off<TN>(j * BKSTEP + bkrow, bncol)] = v;
+    else
+      *(V8*)&Bs[b][(j * 64 + srow) * LDA + scol] = v;
+  };
+  // KRSC fragment addresses (T10 map): lane 4q+pp of 16-lane group fk
+  // supplies row 8 fk + q, columns 4 pp .. 4 pp + 3 of the fragment's 16
+  int boff[NI];
+#pragma unroll
+  for (int ni = 0; ni < NI; ni++)
+    boff[ni] = krsc_off<TN>(fk * 8 + (fr >> 2),
+                            wc * WN + ni * 16 + (fr & 3) * 4);
 
   f32x4 acc[MI][NI] = {};
 
@@ -191,11 +283,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
     *(V8*)&As[0][(j * 64 + srow) * LDA + scol] = a0;
   }
 #pragma unroll
-  for (int j = 0; j < BC; j++) {
-    V8 b0 = load8_b<MODE, VECB>(Bw, p, mg, n0 + j * 64 + srow, kbeg + scol,
-                                Ntot);
-    *(V8*)&Bs[0][(j * 64 + srow) * LDA + scol] = b0;
-  }
+  for (int j = 0; j < BC; j++) store_b(0, j, load_b(j, kbeg));
   V8 a_nx[AC], b_nx[BC];
   if (kbeg + 32 < kend) {
 #pragma unroll
@@ -203,9 +291,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
       a_nx[j] = load8_a<MODE, VECA>(A, p, mg, m0 + j * 64 + srow,
                                     kbeg + 32 + scol);
 #pragma unroll
-    for (int j = 0; j < BC; j++)
-      b_nx[j] = load8_b<MODE, VECB>(Bw, p, mg, n0 + j * 64 + srow,
-                                    kbeg + 32 + scol, Ntot);
+    for (int j = 0; j < BC; j++) b_nx[j] = load_b(j, kbeg + 32);
   }
   __syncthreads();
 
@@ -218,17 +304,14 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
       for (int j = 0; j < AC; j++)
         *(V8*)&As[buf ^ 1][(j * 64 + srow) * LDA + scol] = a_nx[j];
 #pragma unroll
-      for (int j = 0; j < BC; j++)
-        *(V8*)&Bs[buf ^ 1][(j * 64 + srow) * LDA + scol] = b_nx[j];
+      for (int j = 0; j < BC; j++) store_b(buf ^ 1, j, b_nx[j]);
       if (k0 + 64 < kend) {
 #pragma unroll
         for (int j = 0; j < AC; j++)
           a_nx[j] = load8_a<MODE, VECA>(A, p, mg, m0 + j * 64 + srow,
                                         k0 + 64 + scol);
 #pragma unroll
-        for (int j = 0; j < BC; j++)
-          b_nx[j] = load8_b<MODE, VECB>(Bw, p, mg, n0 + j * 64 + srow,
-                                        k0 + 64 + scol, Ntot);
+        for (int j = 0; j < BC; j++) b_nx[j] = load_b(j, k0 + 64);
       }
     }
     bf16x8 af[MI], bf[NI];
@@ -237,9 +320,17 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
       af[mi] =
           *(const bf16x8*)&As[buf][(wr * WM + mi * 16 + fr) * LDA + fk * 8];
 #pragma unroll
-    for (int ni = 0; ni < NI; ni++)
-      bf[ni] =
-          *(const bf16x8*)&Bs[buf][(wc * WN + ni * 16 + fr) * LDA + fk * 8];
+    for (int ni = 0; ni < NI; ni++) {
+      if (KRSC) {
+        // block-uniform: every lane of every wave issues both reads
+        bf16x4 lo = lds_read_tr16(&Bs[buf][boff[ni]]);
+        bf16x4 hi = lds_read_tr16(&Bs[buf][boff[ni] + 4 * TN]);
+        bf[ni] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      } else {
+        bf[ni] =
+            *(const bf16x8*)&Bs[buf][(wc * WN + ni * 16 + fr) * LDA + fk * 8];
+      }
+    }
 #pragma unroll
     for (int mi = 0; mi < MI; mi++)
 #pragma unroll
@@ -899,13 +990,61 @@ extern "C" void launch_conv_fwd_splitk(const void* x, const void* w,
 #undef SK_T
 }
 
-extern "C" void launch_conv_dgrad(const void* dz, const void* w_rsck,
-                                  void* dx, float* ws, int splitk, ConvP p,
-                                  int accum, hipStream_t st) {
+// KRSC-direct dgrad, one tile class: the split / non-split form and the
+// vector flags (A gathers vec8 along ko, B along c).
+template <int TM, int TN>
+static void dgrad_krsc_t(const bf16* A, const bf16* B, bf16* dx, float* ws,
+                         bool split, int splitk, int kchunk, const ConvP& p,
+                         const MagicP& mg, int accum, hipStream_t st) {
+  dim3 grid(cdiv_h(p.C, TN), cdiv_h(p.M, TM), split ? splitk : 1);
+  const bool va = (p.K % 8) == 0, vb = (p.C % 8) == 0;
+#define KRSC_T(VA, VB)                                                      \
+  do {                                                                      \
+    if (split)                                                              \
+      k_conv_mfma<2, VA, VB, false, true, TM, TN, true>                     \
+          <<<grid, 256, 0, st>>>(A, B, nullptr, ws, nullptr, p, mg, p.C,    \
+                                 kchunk, 0);                                \
+    else                                                                    \
+      k_conv_mfma<2, VA, VB, false, false, TM, TN, true>                    \
+          <<<grid, 256, 0, st>>>(A, B, dx, nullptr, nullptr, p, mg, p.C, 0, \
+                                 accum);                                    \
+  } while (0)
+  if (va && vb) KRSC_T(true, true);
+  else if (va) KRSC_T(true, false);
+  else if (vb) KRSC_T(false, true);
+  else KRSC_T(false, false);
+#undef KRSC_T
+}
+
+// w_layout: DGRAD_W_RSCK — `w` is the permuted RSCK image (MODE 2 as ever);
+// DGRAD_W_KRSC — `w` is the KRSC weight itself (transposed-read B path).
+// Tile and split selection do not depend on the layout.
+extern "C" void launch_conv_dgrad(const void* dz, const void* w, void* dx,
+                                  float* ws, int splitk, ConvP p, int accum,
+                                  int w_layout, hipStream_t st) {
   // p here: M = Nb*H*W, Kd = R*S*K, output channels = C
   bool vec = (p.K % 8) == 0;
   auto A = (const bf16*)dz;
-  auto B = (const bf16*)w_rsck;
+  auto B = (const bf16*)w;
+  if (w_layout == DGRAD_W_KRSC) {
+    const bool split = splitk > 1;
+    int kchunk = 0;
+    if (split) {
+      kchunk = cdiv_h(cdiv_h(p.Kd, splitk), 32) * 32;
+      splitk = cdiv_h(p.Kd, kchunk);
+    }
+    MagicP mg = make_magic(p, 2);
+    int tile = pick_tile_dgrad(p.M, p.C);
+#define DISPATCH(TM, TN)                                                  \
+  dgrad_krsc_t<TM, TN>(A, B, (bf16*)dx, ws, split, splitk, kchunk, p, mg, \
+                       accum, st)
+    if (tile == 3) DISPATCH(256, 64);
+    else if (tile == 2) DISPATCH(128, 128);
+    else if (tile == 1) DISPATCH(128, 64);
+    else DISPATCH(64, 64);
+#undef DISPATCH
+    return;
+  }
   if (splitk > 1) {
     int kchunk = cdiv_h(cdiv_h(p.Kd, splitk), 32) * 32;
     splitk = cdiv_h(p.Kd, kchunk);

@@ -73,6 +73,9 @@ static_assert(std::is_trivially_copyable_v<WgradBatchArgs> &&
                   std::is_trivially_copyable_v<WredBatchArgs>,
               "batched wgrad task tables are copied into the kernarg segment");
 
+// Weight layout handed to launch_conv_dgrad.
+enum DgradWLayout { DGRAD_W_RSCK = 0, DGRAD_W_KRSC = 1 };
+
 // ---------------------------------------------------------- magic division --
 inline void magic_u32(unsigned d, unsigned* m, int* sh) {
   if (d <= 1) { *m = 0; *sh = 0; return; }
@@ -126,8 +129,9 @@ void launch_conv_fwd(const void* x, const void* w, void* y, float* stats,
                      ConvP p, hipStream_t st);
 void launch_conv_fwd_splitk(const void* x, const void* w, float* ws, ConvP p,
                             int splitk, hipStream_t st);
-void launch_conv_dgrad(const void* dz, const void* w_rsck, void* dx,
-                       float* ws, int splitk, ConvP p, int accum,
+// w_layout says what `w` is: the RSCK image, or the KRSC weight itself
+void launch_conv_dgrad(const void* dz, const void* w, void* dx, float* ws,
+                       int splitk, ConvP p, int accum, int w_layout,
                        hipStream_t st);
 void launch_gemm_bf16(const void* a, const void* b, void* c, int M, int N,
                       int K, hipStream_t st);

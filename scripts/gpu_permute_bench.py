@@ -1,6 +1,10 @@
 """KRSC->RSCK batched permute isolation bench (flat-engine RSCK refresh).
 
-Usage: HZ_PERMUTE_V2={0,1} python scripts/gpu_permute_bench.py
+Usage: HZ_DGRAD_KRSC=0 HZ_PERMUTE_V2={0,1} python scripts/gpu_permute_bench.py
+
+Run it under HZ_DGRAD_KRSC=0: the default dgrad reads the KRSC weights
+directly, so the manager keeps no RSCK image and refresh_rsck() launches
+nothing (docs/TUNING.md).
 """
 import os
 import sys
