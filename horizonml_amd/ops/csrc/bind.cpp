@@ -51,6 +51,14 @@ bool g_dgrad_krsc = env_long("HZ_DGRAD_KRSC", 1) != 0;
 void set_dgrad_krsc(bool on) { g_dgrad_krsc = on; }
 bool dgrad_krsc_enabled() { return g_dgrad_krsc; }
 
+// Wgrad m-loop body (conv_kernels.hip, "Row-major form").  HZ_WGRAD_TR (read
+// at load, default on) selects row-major LDS images with transposed fragment
+// reads; off = the former transposed 2-byte scatter, bitwise the same dW,
+// kept for A/B timing and as the tests' reference.
+bool g_wgrad_tr = env_long("HZ_WGRAD_TR", 1) != 0;
+void set_wgrad_tr(bool on) { g_wgrad_tr = on; }
+bool wgrad_tr_enabled() { return g_wgrad_tr; }
+
 // ---- deferred (batched) wgrad ---------------------------------------------
 // The weight-gradient GEMMs are off the backward's critical chain (nothing
 // reads dW until the optimizer step), and each conv's own wgrad underfills
@@ -142,7 +150,8 @@ void flush_one_group(int group_lo, int group_hi) {
     // task's blocks so per-task fill matters less than slab volume — at
     // mchunk 512 a ResNet50 layer1 conv makes 196 f32 slabs whose
     // write+reduce traffic dominated wgrad_reduce (r02 traces)
-    const int mc_base = p.M >= 32768 ? 2048 : 512;
+    static const int mc_small = (int)env_long("HZ_WG_MCHUNK", 512);
+    const int mc_base = p.M >= 32768 ? 2048 : mc_small;
     int ms = std::max(1, cdiv_i(p.M, mc_base));
     int mc = cdiv_i(cdiv_i(p.M, ms), 32) * 32;
     ms = cdiv_i(p.M, mc);
@@ -204,7 +213,7 @@ void flush_one_group(int group_lo, int group_hi) {
         t.vec = (pw.p.C % 8) == 0;
         blocks += t.tx * t.ty * t.msplit;
       }
-      launch_wgrad_batched_t(&a, blocks, tk3, tko, st);
+      launch_wgrad_batched_t(&a, blocks, tk3, tko, (int)g_wgrad_tr, st);
     }
   }
 
@@ -578,7 +587,7 @@ std::vector<Tensor> conv_bn_act_bwd(
       ws_ptr = ws.data_ptr<float>();
     }
     launch_wgrad(x.data_ptr(), dconv.data_ptr(), dw.data_ptr<float>(), ws_ptr,
-                 p, st);
+                 p, (int)g_wgrad_tr, st);
   }
 
   TORCH_CHECK(need_dx || !fuse_up.has_value(),
@@ -898,7 +907,7 @@ Tensor wgrad_only(Tensor x, Tensor dz, int64_t K, int64_t R, int64_t S,
       ws_ptr = ws.data_ptr<float>();
     }
     launch_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr<float>(), ws_ptr,
-                 p, cur_stream());
+                 p, (int)g_wgrad_tr, cur_stream());
   }
   return dw;
 }
@@ -1245,4 +1254,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_dgrad_only", &conv_dgrad_only);
   m.def("set_dgrad_krsc", &set_dgrad_krsc);
   m.def("dgrad_krsc_enabled", &dgrad_krsc_enabled);
+  m.def("set_wgrad_tr", &set_wgrad_tr);
+  m.def("wgrad_tr_enabled", &wgrad_tr_enabled);
 }

@@ -163,8 +163,9 @@ DEV V8 load8_b(const bf16* __restrict__ src, const ConvP& p,
 // swizzle moves whole 32-byte chunks, so the 16-byte staging stores and
 // the 8-byte-aligned transposed reads both stay inside one chunk, and the
 // second read of a fragment (rows +4) is the first one's address + 4 rows.
+// The wgrad operand tiles ([32 m][k3], [32 m][ko]) use the same image.
 template <int TN>
-DEV int krsc_off(int k, int n) {
+DEV int lds_tr_off(int k, int n) {
   const int f = TN == 64 ? (((k >> 1) & 1) | (((k >> 3) & 1) << 1))
                          : ((k & 3) | (((k >> 3) & 1) << 2));
   return k * TN + ((((n >> 4) ^ f)) << 4) + (n & 15);
@@ -216,7 +217,7 @@ DEV bf16x4 lds_read_tr16(const bf16* sp) {
 //    tile at ~2% of the bf16 peak on ResNet50@224 (r50_224_pmc_mfma.txt).
 //
 // KRSC (MODE 2 only): B is the KRSC weight; Bs holds the swizzled [32][TN]
-// image of krsc_off() in place of the [TN][LDA] one and the B fragments come
+// image of lds_tr_off() in place of the [TN][LDA] one and the B fragments come
 // from transposed reads.  The A side, the accumulators, the K order and the
 // epilogue are shared with the RSCK form.
 template <int MODE, bool VECA, bool VECB, bool STATS, bool SPLIT,
@@ -235,7 +236,8 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
   constexpr int NI = TN / 32;
   constexpr int WM = TM / 2, WN = TN / 2;
   static_assert(!KRSC || MODE == 2, "KRSC is a dgrad B layout");
-  static_assert(!KRSC || TN == 64 || TN == 128, "krsc_off covers TN 64/128");
+  static_assert(!KRSC || TN == 64 || TN == 128,
+                "lds_tr_off covers TN 64/128");
   __shared__ __attribute__((aligned(16))) bf16 As[2][TM * LDA];
   __shared__ __attribute__((aligned(16))) bf16 Bs[2][TN * LDA];  // ≥ 32*TN
 
@@ -262,7 +264,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
   };
   auto store_b = [&](int b, int j, const V8& v) {
     if (KRSC)
-      *(V8*)&Bs[b][krsc_off<TN>(j * BKSTEP + bkrow, bncol)] = v;
+      *(V8*)&Bs[b][lds_tr_off<TN>(j * BKSTEP + bkrow, bncol)] = v;
     else
       *(V8*)&Bs[b][(j * 64 + srow) * LDA + scol] = v;
   };
@@ -271,7 +273,7 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
   int boff[NI];
 #pragma unroll
   for (int ni = 0; ni < NI; ni++)
-    boff[ni] = krsc_off<TN>(fk * 8 + (fr >> 2),
+    boff[ni] = lds_tr_off<TN>(fk * 8 + (fr >> 2),
                             wc * WN + ni * 16 + (fr & 3) * 4);
 
   f32x4 acc[MI][NI] = {};
@@ -388,11 +390,12 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
 
 // ------------------------------------------------------------------ wgrad --
 // dW[ko][k3] += Σ_m patch(m,k3) · dz(m,ko);  dW is KRSC flat [Ntot][Kd] f32.
-// MFMA formulation: the reduction axis is m, so both operands are staged
-// TRANSPOSED into LDS ([k3][m] and [ko][m]) during the gather (coalesced
-// global vec8 reads, 8 strided b16 LDS writes per thread), which makes the
-// MFMA fragment reads contiguous ds_read_b128.  Output tile 64(k3)×64(ko),
-// m reduced 32-deep per MFMA step, msplit-way M parallelism.
+// MFMA formulation: the reduction axis is m.  In the transposed-scatter
+// form (TR = false) both operands are staged TRANSPOSED into LDS ([k3][m]
+// and [ko][m]) during the gather (coalesced global vec8 reads, 8 strided b16
+// LDS writes per thread), which makes the MFMA fragment reads contiguous
+// ds_read_b128; the row-major form (below) is the default.  Output tile
+// 64(k3)×64(ko), m reduced 32-deep per MFMA step, msplit-way M parallelism.
 //
 // Epilogue is ATOMIC-FREE (measured: the former per-element f32 atomicAdd
 // into dW cost ~12.5 µs per million atomics and dominated wgrad — see
@@ -407,6 +410,27 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
 // backward run as ONE kernel — every task's (tile, z) blocks are in flight
 // together, so the chip fills without oversplitting M, and 2 launches
 // replace ~40 (bind.cpp::flush_wgrad).
+//
+// Row-major form (TR, the default): the operand tiles are [32 m][k3] and
+// [32 m][ko] as they come out of the gather — exactly the shape of dgrad's
+// KRSC B tile (reduction rows × output columns).  Each thread's vec8 goes
+// into the swizzled image of lds_tr_off() with ONE 16-byte store instead of
+// eight swizzled ds_write_b16, and the MFMA fragments (8 consecutive m of one
+// k3 / ko column per lane) are fetched with two ds_read_b64_tr_b16 each, as
+// MODE 2 + KRSC forms bf[ni].  Lane (fr, fk) ends up with rows 8fk..8fk+7 of
+// column fr — what the ds_read_b128 of the transposed image delivers — so
+// operand values, the m order inside an MFMA and the MFMA order are those of
+// the transposed form and dW is bitwise the same.
+//   EXEC rule: the transposed reads run with EXEC all ones.  mbeg/mend, the
+// task lookup and the vec flag are block-uniform and there is no early
+// return; rows ≥ M, k3 ≥ Kd and ko ≥ K are ZEROS in the image (the loaders
+// zero-fill), never masked lanes.
+//   The m-loop keeps one LDS buffer, two barriers per K-step and a one-deep
+// register prefetch: k_conv_mfma's double-buffered loop was built on top of
+// this body and measured no faster for any flagship task (docs/STATUS.md,
+// "Measured negative results").
+// TR == false is the transposed-scatter body, kept for A/B timing and as
+// the bitwise reference of the tests (HZ_WGRAD_TR=0 / set_wgrad_tr(false)).
 #define LDW 40  // 32 m + 8 pad
 
 // TK3: k3-tile width (64 default; 128 for big-Kd large-M convs — halves
@@ -418,11 +442,94 @@ union WgradSmemT {
     bf16 At[TK3 * LDW];  // [k3][m]
     bf16 Dt[TKO * LDW];  // [ko][m]
   } s;
+  struct {  // TR: [32 m][TK3 | TKO], swizzled by lds_tr_off
+    __attribute__((aligned(16))) bf16 A[32 * TK3];
+    __attribute__((aligned(16))) bf16 D[32 * TKO];
+  } r;
   float out[64][TK3 == 64 ? 65 : 131];  // transposed epilogue staging
 };
 using WgradSmem = WgradSmemT<64, 64>;
 
-template <bool VECA, int TK3 = 64, int TKO = 64>
+// m-loop of the row-major form: accumulates rows [mbeg, mend) into acc.
+template <bool VECA, int TK3, int TKO>
+DEV void wgrad_mloop_tr(const bf16* __restrict__ X,
+                        const bf16* __restrict__ Dz, const ConvP& p,
+                        const MagicP& mg, int Ntot, int k3_0, int n0,
+                        int mbeg, int mend, WgradSmemT<TK3, TKO>& smem,
+                        f32x4 (&acc)[TK3 / 32][TKO / 32]) {
+  constexpr int AC = TK3 / 64, DC = TKO / 64;
+  constexpr int MI = TK3 / 32, NI = TKO / 32;
+  const int tid = threadIdx.x;
+  const int sm = tid >> 3, sv = (tid & 7) * 8;  // m row, 8-wide k3/ko chunk
+  const int lane = tid & 63, wave = tid >> 6;
+  const int wr = wave >> 1, wc = wave & 1;
+  const int fr = lane & 15, fk = lane >> 4;
+
+  V8 a_nx[AC], d_nx[DC];
+  // tile with m-origin mt -> registers (zero-filled past M / Kd / K)
+  auto load_tile = [&](int mt) {
+#pragma unroll
+    for (int j = 0; j < AC; j++)
+      a_nx[j] = load8_a<1, VECA>(X, p, mg, mt + sm, k3_0 + j * 64 + sv);
+#pragma unroll
+    for (int j = 0; j < DC; j++) {
+      int m = mt + sm, n = n0 + j * 64 + sv;
+      if (m < p.M && n < Ntot)
+        d_nx[j].u = *(const uint4*)(Dz + (long)m * Ntot + n);
+      else
+        d_nx[j].u = uint4{0, 0, 0, 0};
+    }
+  };
+  bf16* At = smem.r.A;  // [32 m][TK3]
+  bf16* Dt = smem.r.D;  // [32 m][TKO]
+  // fragment addresses (T10 map): lane 4q+pp of 16-lane group fk supplies
+  // row 8 fk + q, columns 4 pp .. 4 pp + 3 of the fragment's 16
+  int aoff[MI], doff[NI];
+#pragma unroll
+  for (int mi = 0; mi < MI; mi++)
+    aoff[mi] = lds_tr_off<TK3>(fk * 8 + (fr >> 2),
+                               wr * (TK3 / 2) + mi * 16 + (fr & 3) * 4);
+#pragma unroll
+  for (int ni = 0; ni < NI; ni++)
+    doff[ni] = lds_tr_off<TKO>(fk * 8 + (fr >> 2),
+                               wc * (TKO / 2) + ni * 16 + (fr & 3) * 4);
+
+  load_tile(mbeg);
+  for (int m0 = mbeg; m0 < mend; m0 += 32) {
+    // registers -> LDS as the tile lies in memory: one 16-byte store a chunk
+#pragma unroll
+    for (int j = 0; j < AC; j++)
+      *(V8*)&At[lds_tr_off<TK3>(sm, j * 64 + sv)] = a_nx[j];
+#pragma unroll
+    for (int j = 0; j < DC; j++)
+      *(V8*)&Dt[lds_tr_off<TKO>(sm, j * 64 + sv)] = d_nx[j];
+    __syncthreads();
+    if (m0 + 32 < mend) load_tile(m0 + 32);
+    // block-uniform: every lane of every wave issues all the reads
+    bf16x8 af[MI], bf[NI];
+#pragma unroll
+    for (int mi = 0; mi < MI; mi++) {
+      bf16x4 lo = lds_read_tr16(&At[aoff[mi]]);
+      bf16x4 hi = lds_read_tr16(&At[aoff[mi] + 4 * TK3]);
+      af[mi] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+#pragma unroll
+    for (int ni = 0; ni < NI; ni++) {
+      bf16x4 lo = lds_read_tr16(&Dt[doff[ni]]);
+      bf16x4 hi = lds_read_tr16(&Dt[doff[ni] + 4 * TKO]);
+      bf[ni] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    }
+#pragma unroll
+    for (int mi = 0; mi < MI; mi++)
+#pragma unroll
+      for (int ni = 0; ni < NI; ni++)
+        acc[mi][ni] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
+    __syncthreads();
+  }
+}
+
+template <bool VECA, int TK3 = 64, int TKO = 64, bool TR = false>
 DEV void wgrad_tile(const bf16* __restrict__ X, const bf16* __restrict__ Dz,
                     float* __restrict__ out, const ConvP& p,
                     const MagicP& mg, int Ntot, int mchunk, int tx, int ty,
@@ -444,6 +551,11 @@ DEV void wgrad_tile(const bf16* __restrict__ X, const bf16* __restrict__ Dz,
 
   f32x4 acc[MI][NI] = {};
 
+  if (TR) {
+    wgrad_mloop_tr<VECA, TK3, TKO>(X, Dz, p, mg, Ntot, k3_0, n0, mbeg, mend,
+                                   smem, acc);
+  } else {
+  // transposed-scatter m-loop, unchanged
   V8 a_nx[AC], d_nx[DC];
 #pragma unroll
   for (int j = 0; j < AC; j++)
@@ -510,6 +622,7 @@ DEV void wgrad_tile(const bf16* __restrict__ X, const bf16* __restrict__ Dz,
             af[mi], bf[ni], acc[mi][ni], 0, 0, 0);
     __syncthreads();
   }
+  }  // !TR
   // D: col (=ko) = fr, row (=k3) = fk*4+q.  Transpose through the 64-ko
   // LDS image, one pass per 64-ko slab (TKO=128: pass p uses only the
   // wc==p waves' accumulators; every thread joins the global store).
@@ -554,13 +667,13 @@ DEV void wgrad_tile(const bf16* __restrict__ X, const bf16* __restrict__ Dz,
   }
 }
 
-template <bool VECA>
+template <bool VECA, bool TR>
 __global__ __launch_bounds__(256) void k_wgrad(
     const bf16* __restrict__ X, const bf16* __restrict__ Dz,
     float* __restrict__ dW, ConvP p, MagicP mg, int Ntot, int mchunk) {
   __shared__ WgradSmem smem;
-  wgrad_tile<VECA, 64, 64>(X, Dz, dW, p, mg, Ntot, mchunk, blockIdx.x,
-                           blockIdx.y, blockIdx.z, gridDim.z > 1, smem);
+  wgrad_tile<VECA, 64, 64, TR>(X, Dz, dW, p, mg, Ntot, mchunk, blockIdx.x,
+                               blockIdx.y, blockIdx.z, gridDim.z > 1, smem);
 }
 
 // Σ over msplit wgrad slabs [z][n] -> dW[n] (+=; dW pre-zeroed or fresh).
@@ -596,7 +709,7 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce(
 // (mchunk ≈ 512 rows) and the grid still fills 256 CUs without atomics.
 // Task tables travel as kernel arguments by value — no staging buffers,
 // hipGraph-capture-safe.  WgradBatchArgs / WredBatchArgs: launch.h.
-template <int TK3, int TKO>
+template <int TK3, int TKO, bool TR>
 __global__ __launch_bounds__(256) void k_wgrad_batched(WgradBatchArgs a) {
   int bid = blockIdx.x;
   int i = 0;
@@ -610,11 +723,11 @@ __global__ __launch_bounds__(256) void k_wgrad_batched(WgradBatchArgs a) {
   const bf16* X = (const bf16*)t.X;
   const bf16* Dz = (const bf16*)t.Dz;
   if (t.vec)
-    wgrad_tile<true, TK3, TKO>(X, Dz, t.out, t.p, t.mg, t.Ntot, t.mchunk, tx,
-                               ty, z, t.msplit > 1, smem);
+    wgrad_tile<true, TK3, TKO, TR>(X, Dz, t.out, t.p, t.mg, t.Ntot, t.mchunk,
+                                   tx, ty, z, t.msplit > 1, smem);
   else
-    wgrad_tile<false, TK3, TKO>(X, Dz, t.out, t.p, t.mg, t.Ntot, t.mchunk,
-                                tx, ty, z, t.msplit > 1, smem);
+    wgrad_tile<false, TK3, TKO, TR>(X, Dz, t.out, t.p, t.mg, t.Ntot, t.mchunk,
+                                    tx, ty, z, t.msplit > 1, smem);
 }
 
 __global__ __launch_bounds__(256) void k_wgrad_reduce_batched(
@@ -1100,18 +1213,27 @@ extern "C" void launch_gemm_bf16(const void* a, const void* b, void* c, int M,
 // tile class per task batch: tx/ty counted in (tk3, tko)-wide tiles by
 // the caller.  128-wide k3 halves Dz re-reads; 128-wide ko halves X
 // re-reads; both double the MFMA per staging write.
-extern "C" void launch_wgrad_batched_t(const WgradBatchArgs* args, int blocks,
-                                       int tk3, int tko, hipStream_t st) {
-  if (blocks <= 0) return;
-  const WgradBatchArgs& a = *args;
+template <bool TR>
+static void wgrad_batched_tr(const WgradBatchArgs& a, int blocks, int tk3,
+                             int tko, hipStream_t st) {
   if (tk3 == 128 && tko == 128)
-    k_wgrad_batched<128, 128><<<blocks, 256, 0, st>>>(a);
+    k_wgrad_batched<128, 128, TR><<<blocks, 256, 0, st>>>(a);
   else if (tk3 == 128)
-    k_wgrad_batched<128, 64><<<blocks, 256, 0, st>>>(a);
+    k_wgrad_batched<128, 64, TR><<<blocks, 256, 0, st>>>(a);
   else if (tko == 128)
-    k_wgrad_batched<64, 128><<<blocks, 256, 0, st>>>(a);
+    k_wgrad_batched<64, 128, TR><<<blocks, 256, 0, st>>>(a);
   else
-    k_wgrad_batched<64, 64><<<blocks, 256, 0, st>>>(a);
+    k_wgrad_batched<64, 64, TR><<<blocks, 256, 0, st>>>(a);
+}
+
+// tr: row-major images + transposed reads (nonzero) or the transposed-scatter
+// body (0).
+extern "C" void launch_wgrad_batched_t(const WgradBatchArgs* args, int blocks,
+                                       int tk3, int tko, int tr,
+                                       hipStream_t st) {
+  if (blocks <= 0) return;
+  if (tr) wgrad_batched_tr<true>(*args, blocks, tk3, tko, st);
+  else wgrad_batched_tr<false>(*args, blocks, tk3, tko, st);
 }
 
 extern "C" void launch_wgrad_reduce_batched(const WredBatchArgs* args,
@@ -1129,19 +1251,25 @@ extern "C" int wgrad_msplit(ConvP p) {
 // ws: per-split slab workspace [msplit][K][Kd] f32 (only read/written when
 // msplit > 1); dw must be pre-zeroed (direct-grad .grad view or fresh).
 extern "C" void launch_wgrad(const void* x, const void* dz, float* dw,
-                             float* ws, ConvP p, hipStream_t st) {
+                             float* ws, ConvP p, int tr, hipStream_t st) {
   int msplit = wgrad_msplit(p);
   int mchunk = cdiv_h(cdiv_h(p.M, msplit), 32) * 32;
   dim3 grid(cdiv_h(p.Kd, 64), cdiv_h(p.K, 64), msplit);
   bool vec = (p.C % 8) == 0;
   float* out = msplit > 1 ? ws : dw;
   MagicP mg = make_magic(p, 1);
-  if (vec)
-    k_wgrad<true><<<grid, 256, 0, st>>>((const bf16*)x, (const bf16*)dz, out,
-                                        p, mg, p.K, mchunk);
-  else
-    k_wgrad<false><<<grid, 256, 0, st>>>((const bf16*)x, (const bf16*)dz,
-                                         out, p, mg, p.K, mchunk);
+#define WGRAD_T(VA, TR)                                               \
+  k_wgrad<VA, TR><<<grid, 256, 0, st>>>((const bf16*)x, (const bf16*)dz, \
+                                        out, p, mg, p.K, mchunk)
+#define DISPATCH(TR)            \
+  do {                          \
+    if (vec) WGRAD_T(true, TR); \
+    else WGRAD_T(false, TR);    \
+  } while (0)
+  if (tr) DISPATCH(true);
+  else DISPATCH(false);
+#undef DISPATCH
+#undef WGRAD_T
   if (msplit > 1) {
     long n = (long)p.K * p.Kd;
     int blocks = (int)min((n / 4 + 255) / 256, (long)1024);

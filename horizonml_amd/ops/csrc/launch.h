@@ -136,10 +136,11 @@ void launch_conv_dgrad(const void* dz, const void* w, void* dx, float* ws,
 void launch_gemm_bf16(const void* a, const void* b, void* c, int M, int N,
                       int K, hipStream_t st);
 int wgrad_msplit(ConvP p);
+// tr != 0: row-major LDS images with transposed reads; 0: transposed scatter
 void launch_wgrad(const void* x, const void* dz, float* dw, float* ws,
-                  ConvP p, hipStream_t st);
+                  ConvP p, int tr, hipStream_t st);
 void launch_wgrad_batched_t(const WgradBatchArgs* args, int blocks, int tk3,
-                            int tko, hipStream_t st);
+                            int tko, int tr, hipStream_t st);
 void launch_wgrad_reduce_batched(const WredBatchArgs* args, int blocks,
                                  hipStream_t st);
 
