@@ -28,7 +28,9 @@ def run_data_parallel(world_size: int, epochs: int, sample_size: int,
                       lr_milestones=(), lr_gamma: float = 0.1,
                       weight_decay: float = 0.0, nesterov: bool = False,
                       decoupled_wd: bool = False,
-                      label_smoothing: float = 0.0):
+                      label_smoothing: float = 0.0,
+                      no_decay_1d: bool = False, clip_grad_norm: float = 0.0,
+                      lars: bool = False, lars_eta: float = 1e-3):
     """Launcher parity with reference ``run_data_parallel``
     (``data_parallel_train.py:233-291``). Returns the combined DataFrame.
 
@@ -36,7 +38,11 @@ def run_data_parallel(world_size: int, epochs: int, sample_size: int,
     ``augment_pad`` zero padding + horizontal flip, fused into the on-device
     normalize.  ``lr_schedule`` … ``label_smoothing`` (extensions too): the
     training-recipe knobs of ``engine.dp.train_dp_flat``; epoch quantities
-    are converted to steps with the rank's loader length."""
+    are converted to steps with the rank's loader length.  ``no_decay_1d``
+    (no weight decay on BN and bias parameters), ``clip_grad_norm`` (global
+    L2 norm, 0 = off), ``lars`` / ``lars_eta`` (SGD only) likewise."""
+    if lars and optimizer_name.lower() == "adam":
+        raise ValueError("lars needs optimizer_name='sgd'")
     return run_workers(dp_worker, world_size, epochs, sample_size, logs_dir,
                        timeout_base=120,
                        extra_args=(batch_size, model_name, backend, synthetic,
@@ -46,10 +52,11 @@ def run_data_parallel(world_size: int, epochs: int, sample_size: int,
                                    warmup_epochs, min_lr,
                                    tuple(lr_milestones), lr_gamma,
                                    weight_decay, nesterov, decoupled_wd,
-                                   label_smoothing))
+                                   label_smoothing, no_decay_1d,
+                                   clip_grad_norm, lars, lars_eta))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="Data-parallel training")
     ap.add_argument("--world_size", type=int, default=5)
     ap.add_argument("--epochs", type=int, default=5)
@@ -99,14 +106,33 @@ def main():
     ap.add_argument("--lr_gamma", type=float, default=0.1)
     ap.add_argument("--weight_decay", type=float, default=0.0,
                     help="L2 weight decay on every parameter (BN and bias "
-                         "included)")
+                         "included, unless --no_decay_1d)")
     ap.add_argument("--nesterov", action="store_true",
                     help="Nesterov momentum (with --optimizer sgd)")
     ap.add_argument("--decoupled_wd", action="store_true",
                     help="AdamW: decoupled weight decay (with --optimizer "
                          "adam)")
     ap.add_argument("--label_smoothing", type=float, default=0.0)
-    args = ap.parse_args()
+    ap.add_argument("--no_decay_1d", action="store_true",
+                    help="no weight decay on 1-D parameters (BN weight/bias, "
+                         "biases)")
+    ap.add_argument("--clip_grad_norm", type=float, default=0.0,
+                    help="clip the gradient to this global L2 norm "
+                         "(0 = off)")
+    ap.add_argument("--lars", action="store_true",
+                    help="LARS layer-wise trust ratio (with --optimizer sgd)")
+    ap.add_argument("--lars_eta", type=float, default=1e-3,
+                    help="LARS trust coefficient")
+    args = ap.parse_args(argv)
+    if args.lars and args.optimizer == "adam":
+        ap.error("--lars needs --optimizer sgd")
+    if args.clip_grad_norm < 0 or args.lars_eta <= 0:
+        ap.error("--clip_grad_norm must be >= 0 and --lars_eta > 0")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if args.deterministic:
         import os
         os.environ["HZ_DETERMINISTIC"] = "1"
@@ -119,7 +145,9 @@ def main():
                            args.warmup_epochs, args.min_lr,
                            args.lr_milestones, args.lr_gamma,
                            args.weight_decay, args.nesterov,
-                           args.decoupled_wd, args.label_smoothing)
+                           args.decoupled_wd, args.label_smoothing,
+                           args.no_decay_1d, args.clip_grad_norm, args.lars,
+                           args.lars_eta)
     if df is not None:
         print(df.tail(args.world_size).to_string(index=False))
 

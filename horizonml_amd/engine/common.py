@@ -121,13 +121,35 @@ def build_engine_optimizer(module, params, name: str, lr: float, device):
     return build_optimizer(params, name, lr=lr)
 
 
+def decay_param_groups(model, weight_decay: float):
+    """Torch param groups that keep weight decay off ``ndim <= 1`` parameters
+    (BN weight/bias, linear/conv biases): ``[decay, no_decay]``, the second
+    with ``weight_decay=0``.  Depthwise conv weights have ``ndim > 1`` and decay.  The
+    flat engine's ``no_decay_1d`` draws the same line."""
+    params = [p for p in model.parameters() if p.requires_grad]
+    return [{"params": [p for p in params if p.ndim > 1],
+             "weight_decay": weight_decay},
+            {"params": [p for p in params if p.ndim <= 1],
+             "weight_decay": 0.0}]
+
+
 def build_optimizer(params, name: str = "adam", lr: float = 1e-3,
                     momentum: float = 0.9, weight_decay: float = 0.0,
-                    nesterov: bool = False, decoupled_wd: bool = False):
+                    nesterov: bool = False, decoupled_wd: bool = False,
+                    lars: bool = False, lars_eta: float = 1e-3):
     """Reference default: Adam(lr=1e-3) (``data_parallel_train.py:205``).
     The north star also names the SGD step — both supported.
-    ``decoupled_wd`` selects ``torch.optim.AdamW``."""
+    ``decoupled_wd`` selects ``torch.optim.AdamW``.  ``lars`` (SGD only)
+    selects ``engine.lars.LARS``.  ``params`` may be the groups of
+    ``decay_param_groups``."""
     name = name.lower()
+    if lars:
+        if name != "sgd":
+            raise ValueError("lars needs the sgd optimizer")
+        from .lars import LARS
+        return LARS(params, lr=lr, momentum=momentum,
+                    weight_decay=weight_decay, nesterov=nesterov,
+                    eta=lars_eta)
     # foreach=True batches the per-parameter update into multi-tensor
     # kernels — the eager engine paths are launch-bound otherwise
     if name == "adam":

@@ -26,7 +26,8 @@ import torch.nn.functional as F
 
 from ..data import get_dataloader
 from ..engine.common import (GradDivergenceProbe, Meters,
-                             build_optimizer, build_schedule, progress_iter)
+                             build_optimizer, build_schedule,
+                             decay_param_groups, progress_iter)
 from ..models import build_model
 from ..parallel import BucketedDataParallel
 from ..profiling.metrics import (EpochMetrics, MetricsWriter,
@@ -90,7 +91,9 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
                   lr_schedule: str = "constant", warmup_epochs: float = 0.0,
                   min_lr: float = 0.0, lr_milestones=(), lr_gamma: float = 0.1,
                   weight_decay: float = 0.0, nesterov: bool = False,
-                  decoupled_wd: bool = False, label_smoothing: float = 0.0):
+                  decoupled_wd: bool = False, label_smoothing: float = 0.0,
+                  no_decay_1d: bool = False, clip_grad_norm: float = 0.0,
+                  lars: bool = False, lars_eta: float = 1e-3):
     """DP training on the flat fast path — the entrypoint-facing version of
     the bench.py flagship step (the parity entrypoint
     should run the best path we have).
@@ -128,6 +131,13 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
     fused kernels, ``label_smoothing`` the fused cross-entropy.  All default
     to the unscheduled step, which launches the same kernels as before.
 
+    ``no_decay_1d`` / ``clip_grad_norm`` / ``lars`` / ``lars_eta`` go to the
+    Horizon optimizers, which then step through the segmented kernels; the
+    norm reduction of clipping and LARS (2 dispatches) runs inside the
+    captured optimizer step.  With world > 1 the norms are taken over the
+    averaged gradient (the all-reduced bf16 buffer x 1/world) on every rank
+    by the same fixed-order reduction, so replicas stay identical.
+
     Capture runs 3 warmup steps on the first batch shape; parameter /
     BN-buffer / optimizer state is snapshotted before and restored after,
     so training still starts from the seeded init.  Ragged final batches
@@ -150,11 +160,18 @@ def train_dp_flat(ctx: DistContext, epochs: int, sample_size: int,
     mgr = FlatParamManager(model, dev)
     sched = build_schedule(lr_schedule, lr, epochs, len(loader),
                            warmup_epochs, min_lr, lr_milestones, lr_gamma)
+    if lars and optimizer_name == "adam":
+        raise ValueError("lars needs the sgd optimizer")
     opt = (HorizonAdam(mgr, lr=lr, weight_decay=weight_decay,
-                       schedule=sched, decoupled_wd=decoupled_wd)
+                       schedule=sched, decoupled_wd=decoupled_wd,
+                       no_decay_1d=no_decay_1d,
+                       clip_grad_norm=clip_grad_norm)
            if optimizer_name == "adam"
            else HorizonSGD(mgr, lr=lr, weight_decay=weight_decay,
-                           schedule=sched, nesterov=nesterov))
+                           schedule=sched, nesterov=nesterov,
+                           no_decay_1d=no_decay_1d,
+                           clip_grad_norm=clip_grad_norm, lars=lars,
+                           lars_eta=lars_eta))
     import torch.distributed as dist
     force_comm = (os.environ.get("HZ_FORCE_COMM") == "1" and world == 1
                   and dist.is_initialized() and ctx.backend == "nccl")
@@ -381,8 +398,15 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
              lr_schedule: str = "constant", warmup_epochs: float = 0.0,
              min_lr: float = 0.0, lr_milestones=(), lr_gamma: float = 0.1,
              weight_decay: float = 0.0, nesterov: bool = False,
-             decoupled_wd: bool = False, label_smoothing: float = 0.0):
+             decoupled_wd: bool = False, label_smoothing: float = 0.0,
+             no_decay_1d: bool = False, clip_grad_norm: float = 0.0,
+             lars: bool = False, lars_eta: float = 1e-3):
     """Run the DP training loop for this rank; writes the per-worker CSV.
+
+    ``no_decay_1d``: torch param groups from ``decay_param_groups``.
+    ``clip_grad_norm`` (> 0): ``torch.nn.utils.clip_grad_norm_`` on the
+    averaged gradient, between the all-reduce and the step.  ``lars``: the
+    optimizer is ``engine.lars.LARS``.
 
     ``per_step_barrier=True`` restores the reference's full-world barrier
     after EVERY step (``data_parallel_train.py:150-152``) so ``idle_time``
@@ -403,9 +427,11 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
     if ctx.is_gpu:
         model = model.to(ctx.device)
     ddp = BucketedDataParallel(model, profiler=None)
-    optimizer = build_optimizer(model.parameters(), optimizer_name, lr=lr,
-                                weight_decay=weight_decay, nesterov=nesterov,
-                                decoupled_wd=decoupled_wd)
+    optimizer = build_optimizer(
+        decay_param_groups(model, weight_decay) if no_decay_1d
+        else model.parameters(), optimizer_name, lr=lr,
+        weight_decay=weight_decay, nesterov=nesterov,
+        decoupled_wd=decoupled_wd, lars=lars, lars_eta=lars_eta)
     sched = build_schedule(lr_schedule, lr, epochs, len(loader),
                            warmup_epochs, min_lr, lr_milestones, lr_gamma)
     probe = GradDivergenceProbe(model.parameters()) if probe_divergence else None
@@ -464,6 +490,9 @@ def train_dp(ctx: DistContext, epochs: int, sample_size: int, logs_dir: str,
             with prof.comm():
                 ddp.finalize_backward()
             with prof.compute():
+                if clip_grad_norm > 0:
+                    torch.nn.utils.clip_grad_norm_(model.parameters(),
+                                                   clip_grad_norm)
                 optimizer.step()
                 if ctx.is_gpu:
                     from ..models import refresh_all_shadows
@@ -514,15 +543,18 @@ def dp_worker(rank: int, world_size: int, epochs: int, sample_size: int,
               lr_schedule: str = "constant", warmup_epochs: float = 0.0,
               min_lr: float = 0.0, lr_milestones=(), lr_gamma: float = 0.1,
               weight_decay: float = 0.0, nesterov: bool = False,
-              decoupled_wd: bool = False, label_smoothing: float = 0.0):
+              decoupled_wd: bool = False, label_smoothing: float = 0.0,
+              no_decay_1d: bool = False, clip_grad_norm: float = 0.0,
+              lars: bool = False, lars_eta: float = 1e-3):
     """Spawned worker entry (reference ``data_parallel_train.py:192-230``).
 
     ``engine``: ``flat`` (default on GPU via ``auto``) runs the hipGraph /
     fused-step fast path; ``eager`` the bucketed-DDP torch-optimizer loop.
     ``checkpoint_path``: save per epoch (rank 0) and resume when the file
     exists — an extension over the reference.
-    The schedule / weight-decay / Nesterov / AdamW / label-smoothing knobs
-    go to whichever engine runs (see ``train_dp_flat``)."""
+    The schedule / weight-decay / Nesterov / AdamW / label-smoothing /
+    no-decay / clipping / LARS knobs go to whichever engine runs (see
+    ``train_dp_flat``)."""
     ctx = setup_distributed(rank, world_size, port, backend=backend)
     try:
         if ctx.is_gpu and model_name.startswith("resnet"):
@@ -542,7 +574,10 @@ def dp_worker(rank: int, world_size: int, epochs: int, sample_size: int,
                           min_lr=min_lr, lr_milestones=lr_milestones,
                           lr_gamma=lr_gamma, weight_decay=weight_decay,
                           nesterov=nesterov, decoupled_wd=decoupled_wd,
-                          label_smoothing=label_smoothing)
+                          label_smoothing=label_smoothing,
+                          no_decay_1d=no_decay_1d,
+                          clip_grad_norm=clip_grad_norm, lars=lars,
+                          lars_eta=lars_eta)
         else:
             train_dp(ctx, epochs, sample_size, logs_dir,
                      batch_size=batch_size, model_name=model_name,
@@ -555,6 +590,8 @@ def dp_worker(rank: int, world_size: int, epochs: int, sample_size: int,
                      min_lr=min_lr, lr_milestones=lr_milestones,
                      lr_gamma=lr_gamma, weight_decay=weight_decay,
                      nesterov=nesterov, decoupled_wd=decoupled_wd,
-                     label_smoothing=label_smoothing)
+                     label_smoothing=label_smoothing,
+                     no_decay_1d=no_decay_1d, clip_grad_norm=clip_grad_norm,
+                     lars=lars, lars_eta=lars_eta)
     finally:
         teardown_distributed(ctx)

@@ -14,6 +14,11 @@ buffers, single-kernel updates):
   buffer hold RSCK weight images, refreshed by one batched permute kernel
   per step.
 * DP gradient sync becomes ONE bf16 all-reduce of the flat buffer.
+* Anything that depends on which parameter an element belongs to (no weight
+  decay on 1-D parameters, global-norm clipping, the LARS trust ratio) goes
+  through a segment table: one segment per parameter, cut into chunks of at
+  most ``SEG_CHUNK`` elements, one workgroup per chunk (docs/KERNELS.md,
+  "Segmented step").  Built only when an optimizer asks for it.
 """
 from __future__ import annotations
 
@@ -26,8 +31,91 @@ from .. import ops as _ops
 from ..models.layers import ConvBNAct, DepthwiseConvBNAct, Linear
 
 
+SEG_CHUNK = 4096  # elements per chunk = per workgroup of the *_seg kernels
+
+
+class SegmentTable:
+    """Device tables of a segmented flat buffer.
+
+    ``sizes[s]`` elements per segment, in buffer order; ``decay[s]`` /
+    ``adapt[s]`` the contract's static flags.  ``chunks`` int32
+    ``[nchunks, 3] = (segment, start, length)`` with ``length <= chunk`` and
+    no chunk crossing a segment; ``seg_meta`` int32 ``[nseg, 3] = (first
+    chunk, one past the last chunk, decay | adapt << 1)``.  Both are correct
+    by construction: the kernels index the flat buffers with them unchecked."""
+
+    def __init__(self, sizes, decay, adapt, device, chunk: int = SEG_CHUNK):
+        sizes = [int(n) for n in sizes]
+        if not sizes or min(sizes) < 1 or chunk < 1:
+            raise ValueError("segments must be non-empty")
+        if not len(sizes) == len(decay) == len(adapt):
+            raise ValueError("one decay and one adapt flag per segment")
+        if sum(sizes) >= 2 ** 31:
+            raise ValueError("segment offsets are int32")
+        chunks, meta, bounds = [], [], [0]
+        for s, n in enumerate(sizes):
+            b, c0 = bounds[-1], len(chunks)
+            for o in range(0, n, chunk):
+                chunks.append((s, b + o, min(chunk, n - o)))
+            meta.append((c0, len(chunks),
+                         int(bool(decay[s])) | int(bool(adapt[s])) << 1))
+            bounds.append(b + n)
+        self.sizes, self.bounds = sizes, bounds
+        self.decay = [bool(d) for d in decay]
+        self.adapt = [bool(a) for a in adapt]
+        self.numel, self.nseg, self.nchunks = bounds[-1], len(sizes), len(chunks)
+        self.chunks = torch.tensor(chunks, dtype=torch.int32, device=device)
+        self.seg_meta = torch.tensor(meta, dtype=torch.int32, device=device)
+
+    def static_mul(self, wd: float) -> torch.Tensor:
+        """``seg_mul`` with nothing data-dependent in it: ``(1, wd*decay_s)``."""
+        return torch.tensor([(1.0, wd if d else 0.0) for d in self.decay],
+                            dtype=torch.float32, device=self.chunks.device)
+
+
+class _SegState:
+    """What a Horizon optimizer holds once it steps through the segmented
+    kernels: the table, ``seg_mul`` and, with clipping or LARS, the buffers
+    of the per-step norm reduction."""
+
+    def __init__(self, mgr, wd, no_decay_1d, max_norm, lars, eta):
+        self.table = t = mgr.segment_table(no_decay_1d)
+        self.wd, self.max_norm = float(wd), float(max_norm)
+        self.lars, self.eta = bool(lars), float(eta)
+        self.seg_mul = t.static_mul(self.wd)
+        self.dynamic = self.max_norm > 0 or self.lars
+        if self.dynamic:
+            dev = mgr.master.device
+            self.partials = torch.zeros(t.nchunks, 2, device=dev)
+            self.seg_norms = torch.zeros(t.nseg, 2, device=dev)
+            self.norm_out = torch.zeros(2, device=dev)
+
+    def reduce(self, ext, mgr, grad_bf16, grad_scale):
+        """partials + finalize: 2 dispatches, refills ``seg_mul``."""
+        if self.dynamic:
+            ext.seg_norms(mgr.master, mgr.grad, self.table.chunks,
+                          self.table.seg_meta, self.partials, self.seg_norms,
+                          self.seg_mul, self.norm_out, self.wd, self.max_norm,
+                          self.lars, self.eta, grad_bf16, grad_scale)
+
+    def last_grad_norm(self) -> float:
+        if not self.dynamic:
+            raise RuntimeError("the gradient norm is only computed with "
+                               "clip_grad_norm > 0 or lars")
+        return float(self.norm_out[0].cpu())
+
+
+def _seg_state(mgr, wd, no_decay_1d, max_norm, lars=False, eta=1e-3):
+    if max_norm < 0 or eta <= 0:
+        raise ValueError("clip_grad_norm must be >= 0 and lars_eta > 0")
+    if not (no_decay_1d or max_norm > 0 or lars):
+        return None
+    return _SegState(mgr, wd, no_decay_1d, max_norm, lars, eta)
+
+
 class FlatParamManager:
     def __init__(self, model: nn.Module, device: torch.device):
+        self._seg_tables = {}
         # managed convs defer their weight-grad GEMMs: flush_wgrad() (called
         # by the fused optimizer step) runs them as one batched kernel
         _ops.extension().set_wgrad_defer(True)
@@ -108,6 +196,20 @@ class FlatParamManager:
     def zero_grad(self):
         self.grad.zero_()
 
+    def segment_table(self, no_decay_1d: bool = False) -> SegmentTable:
+        """One segment per parameter, in buffer order.  ``adapt_s = 0`` for
+        ``ndim <= 1`` (BN weight/bias, linear/conv biases; depthwise conv
+        weights are not); ``decay_s = 0`` for the same class when
+        ``no_decay_1d``.  Built on first use and kept."""
+        key = bool(no_decay_1d)
+        if key not in self._seg_tables:
+            one_d = [p.ndim <= 1 for p in self.params]
+            self._seg_tables[key] = SegmentTable(
+                [p.numel() for p in self.params],
+                [not (key and d) for d in one_d], [not d for d in one_d],
+                self.master.device)
+        return self._seg_tables[key]
+
 
 def _sched_buffers(schedule, dev):
     """Device residents of a scheduled optimizer: the f32 lr table the kernel
@@ -127,13 +229,22 @@ class HorizonAdam:
     captured step walks the schedule under graph replay, and ``lr`` is
     unused.  ``decoupled_wd``: AdamW (``w *= 1 - lr*wd`` instead of
     ``g += wd*w``).  With neither, ``step`` launches ``k_adam_step`` as
-    before."""
+    before.
+
+    ``no_decay_1d``: no weight decay on ``ndim <= 1`` parameters.
+    ``clip_grad_norm`` (> 0): scale the gradient so its global L2 norm is at
+    most this, ``torch.nn.utils.clip_grad_norm_``'s definition; the norm is
+    reduced on the device inside the step (2 added dispatches).  Either one
+    routes ``step`` through ``k_adam_step_seg``; with neither, nothing is
+    allocated and the branches above run as they are."""
 
     def __init__(self, mgr: FlatParamManager, lr: float = 1e-3,
                  betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 0.0, schedule=None,
-                 decoupled_wd: bool = False):
+                 decoupled_wd: bool = False, no_decay_1d: bool = False,
+                 clip_grad_norm: float = 0.0):
         self.mgr = mgr
+        self.seg = _seg_state(mgr, weight_decay, no_decay_1d, clip_grad_norm)
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.schedule, self.decoupled = schedule, bool(decoupled_wd)
         dev = mgr.master.device
@@ -152,7 +263,16 @@ class HorizonAdam:
         ext = _ops.extension()
         ext.flush_wgrad()  # batched deferred weight grads
         p0, p1, p2 = probe if probe is not None else (None, None, None)
-        if self.schedule is None and not self.decoupled:
+        if self.seg is not None:
+            self.seg.reduce(ext, self.mgr, grad_bf16, grad_scale)
+            ext.adam_step_seg(self.mgr.master, self.mgr.grad, self.m, self.v,
+                              self.mgr.shadow, self.step_t, self.lr_table,
+                              self.lr_out, self.lr, self.betas[0],
+                              self.betas[1], self.eps, self.decoupled,
+                              zero_grad, self.seg.table.chunks,
+                              self.seg.seg_mul, self.mgr.stats_arena,
+                              grad_bf16, grad_scale, p0, p1, p2)
+        elif self.schedule is None and not self.decoupled:
             ext.adam_step(self.mgr.master, self.mgr.grad, self.m,
                           self.v, self.mgr.shadow, self.step_t,
                           self.lr, self.betas[0], self.betas[1],
@@ -175,6 +295,14 @@ class HorizonAdam:
         if self.lr_out is None:
             return float(self.lr)
         return float(self.lr_out.cpu())
+
+    def last_grad_norm(self) -> float:
+        """Global L2 norm of the gradient the last update saw, before
+        clipping.  Syncs — not for the hot loop."""
+        if self.seg is None:
+            raise RuntimeError("the gradient norm is only computed with "
+                               "clip_grad_norm > 0 or lars")
+        return self.seg.last_grad_norm()
 
     def set_step(self, n: int):
         """Position the update counter: the next ``step`` is update ``n``
@@ -202,14 +330,24 @@ class HorizonSGD:
     owns an f32 device ``step_t``, bumped by a one-thread kernel in front of
     the update (one added dispatch per step).  ``nesterov``: torch's
     definition (``w -= lr*(g + mu*u)``).  With neither, ``step`` launches
-    ``k_sgd_step`` alone as before."""
+    ``k_sgd_step`` alone as before.
+
+    ``no_decay_1d`` / ``clip_grad_norm``: as for ``HorizonAdam``.  ``lars``:
+    layer-wise trust ratio ``lars_eta*|w| / (|g| + wd*|w| + 1e-8)`` on every
+    ``ndim > 1`` parameter (``engine.lars.LARS`` is the same contract in
+    plain torch).  Any of them routes ``step`` through ``k_sgd_step_seg``;
+    clipping and LARS add the 2-dispatch norm reduction in front of it."""
 
     def __init__(self, mgr: FlatParamManager, lr: float = 0.1,
                  momentum: float = 0.9, weight_decay: float = 0.0,
-                 schedule=None, nesterov: bool = False):
+                 schedule=None, nesterov: bool = False,
+                 no_decay_1d: bool = False, clip_grad_norm: float = 0.0,
+                 lars: bool = False, lars_eta: float = 1e-3):
         if nesterov and not momentum > 0:
             raise ValueError("nesterov needs momentum > 0")
         self.mgr = mgr
+        self.seg = _seg_state(mgr, weight_decay, no_decay_1d, clip_grad_norm,
+                              lars, lars_eta)
         self.lr, self.mu, self.wd = lr, momentum, weight_decay
         self.schedule, self.nesterov = schedule, bool(nesterov)
         self.mom = (torch.zeros_like(mgr.master) if momentum > 0 else None)
@@ -225,7 +363,15 @@ class HorizonSGD:
         ext = _ops.extension()
         ext.flush_wgrad()  # batched deferred weight grads
         p0, p1, p2 = probe if probe is not None else (None, None, None)
-        if self.schedule is None and not self.nesterov:
+        if self.seg is not None:
+            self.seg.reduce(ext, self.mgr, grad_bf16, grad_scale)
+            ext.sgd_step_seg(self.mgr.master, self.mgr.grad, self.mom,
+                             self.mgr.shadow, self.step_t, self.lr_table,
+                             self.lr_out, self.lr, self.mu, self.nesterov,
+                             zero_grad, self.seg.table.chunks,
+                             self.seg.seg_mul, grad_bf16, grad_scale,
+                             p0, p1, p2)
+        elif self.schedule is None and not self.nesterov:
             ext.sgd_step(self.mgr.master, self.mgr.grad, self.mom,
                          self.mgr.shadow, self.lr, self.mu, self.wd,
                          zero_grad, grad_bf16, grad_scale,
@@ -245,6 +391,14 @@ class HorizonSGD:
         if self.lr_out is None:
             return float(self.lr)
         return float(self.lr_out.cpu())
+
+    def last_grad_norm(self) -> float:
+        """Global L2 norm of the gradient the last update saw, before
+        clipping.  Syncs — not for the hot loop."""
+        if self.seg is None:
+            raise RuntimeError("the gradient norm is only computed with "
+                               "clip_grad_norm > 0 or lars")
+        return self.seg.last_grad_norm()
 
     def set_step(self, n: int):
         """Position the schedule: the next ``step`` is update ``n`` (0-based).

@@ -1042,6 +1042,148 @@ void sgd_step_sched(Tensor master, Tensor grad, c10::optional<Tensor> mom,
                      nesterov ? 1 : 0, cur_stream());
 }
 
+// Segmented forms.  chunks int32 [nchunks,3] = (segment, start, length) and
+// seg_meta int32 [nseg,3] = (chunk begin, chunk end, flags) come from
+// engine/flat.build_segment_table, which is correct by construction; the
+// device tables are not re-read here.  seg_mul f32 [nseg,2].
+struct SegTable {
+  const int* chunks;
+  int nchunks;
+  const float* seg_mul;
+  int nseg;
+};
+
+SegTable seg_table(const Tensor& chunks, const Tensor& seg_mul,
+                   const Tensor& master) {
+  TORCH_CHECK(chunks.scalar_type() == torch::kInt32 && chunks.dim() == 2
+                  && chunks.size(1) == 3 && chunks.size(0) >= 1
+                  && chunks.is_contiguous()
+                  && chunks.device() == master.device(),
+              "chunks must be a contiguous int32 [nchunks,3] tensor on "
+              "master's device");
+  check_f32(seg_mul, "seg_mul");
+  TORCH_CHECK(seg_mul.dim() == 2 && seg_mul.size(1) == 2
+                  && seg_mul.size(0) >= 1 && seg_mul.is_contiguous()
+                  && seg_mul.device() == master.device(),
+              "seg_mul must be a contiguous f32 [nseg,2] tensor on master's "
+              "device");
+  return {chunks.data_ptr<int>(), (int)chunks.size(0),
+          seg_mul.data_ptr<float>(), (int)seg_mul.size(0)};
+}
+
+void seg_norms(Tensor master, Tensor grad, Tensor chunks, Tensor seg_meta,
+               Tensor partials, Tensor seg_norms_out, Tensor seg_mul,
+               Tensor norm_out, double wd, double max_norm, bool lars,
+               double eta, c10::optional<Tensor> grad_bf16,
+               double grad_scale) {
+  check_f32(master, "master");
+  check_f32(grad, "grad");
+  check_f32(partials, "partials");
+  check_f32(seg_norms_out, "seg_norms");
+  check_f32(norm_out, "norm_out");
+  SegTable t = seg_table(chunks, seg_mul, master);
+  TORCH_CHECK(grad.numel() == master.numel(), "grad must match master");
+  TORCH_CHECK(seg_meta.scalar_type() == torch::kInt32
+                  && seg_meta.is_contiguous() && seg_meta.dim() == 2
+                  && seg_meta.size(0) == t.nseg && seg_meta.size(1) == 3
+                  && seg_meta.device() == master.device(),
+              "seg_meta must be a contiguous int32 [nseg,3] tensor on "
+              "master's device");
+  TORCH_CHECK(partials.numel() == 2L * t.nchunks
+                  && seg_norms_out.numel() == 2L * t.nseg
+                  && norm_out.numel() == 2 && partials.is_contiguous()
+                  && seg_norms_out.is_contiguous()
+                  && partials.device() == master.device()
+                  && seg_norms_out.device() == master.device()
+                  && norm_out.device() == master.device(),
+              "partials [nchunks,2], seg_norms [nseg,2], norm_out [2] on "
+              "master's device");
+  TORCH_CHECK(!grad_bf16.has_value()
+                  || (grad_bf16->scalar_type() == torch::kBFloat16
+                      && grad_bf16->numel() == master.numel()),
+              "grad_bf16 must be a bf16 tensor of master's size");
+  // the kernel's 16-byte vector loads index from these bases
+  TORCH_CHECK((uintptr_t)master.data_ptr() % 16 == 0
+                  && (uintptr_t)grad.data_ptr() % 16 == 0
+                  && (!grad_bf16.has_value()
+                      || (uintptr_t)grad_bf16->data_ptr() % 16 == 0),
+              "master / grad / grad_bf16 must be 16-byte aligned");
+  launch_seg_norms(master.data_ptr<float>(), grad.data_ptr<float>(),
+                   opt_ptr(grad_bf16), (float)grad_scale, t.chunks,
+                   t.nchunks, seg_meta.data_ptr<int>(), t.nseg,
+                   partials.data_ptr<float>(),
+                   seg_norms_out.data_ptr<float>(),
+                   seg_mul.data_ptr<float>(), norm_out.data_ptr<float>(),
+                   (float)wd, (float)max_norm, lars ? 1 : 0, (float)eta,
+                   cur_stream());
+}
+
+void adam_step_seg(Tensor master, Tensor grad, Tensor m, Tensor v,
+                   c10::optional<Tensor> shadow, Tensor step_t,
+                   c10::optional<Tensor> lr_table,
+                   c10::optional<Tensor> lr_out, double lr, double b1,
+                   double b2, double eps, bool decoupled, bool zero_grad,
+                   Tensor chunks, Tensor seg_mul,
+                   c10::optional<Tensor> extra_zero,
+                   c10::optional<Tensor> grad_bf16, double grad_scale,
+                   c10::optional<Tensor> probe_prev,
+                   c10::optional<Tensor> probe_sumsq,
+                   c10::optional<Tensor> probe_out) {
+  check_f32(master, "master");
+  check_probe(probe_prev, probe_sumsq, probe_out);
+  TORCH_CHECK(grad.numel() == master.numel() && m.numel() == master.numel()
+                  && v.numel() == master.numel(),
+              "grad / m / v must match master's size");
+  SegTable t = seg_table(chunks, seg_mul, master);
+  long T = 0;
+  const float* table = sched_table(lr_table, master, &T);
+  float* out = sched_scalar(lr_out, master, "lr_out");
+  float* st = sched_scalar(step_t, master, "step_t");
+  launch_adam_step_seg(master.data_ptr<float>(), grad.data_ptr<float>(),
+                       m.data_ptr<float>(), v.data_ptr<float>(),
+                       opt_ptr(shadow), st, (float)lr, (float)b1, (float)b2,
+                       (float)eps, zero_grad ? 1 : 0,
+                       opt_ptr<float>(extra_zero),
+                       extra_zero.has_value() ? extra_zero->numel() : 0,
+                       opt_ptr(grad_bf16), (float)grad_scale,
+                       opt_ptr<float>(probe_prev),
+                       opt_ptr<float>(probe_sumsq), opt_ptr<float>(probe_out),
+                       table, T, out, decoupled ? 1 : 0, t.chunks, t.nchunks,
+                       t.seg_mul, cur_stream());
+}
+
+void sgd_step_seg(Tensor master, Tensor grad, c10::optional<Tensor> mom,
+                  c10::optional<Tensor> shadow, c10::optional<Tensor> step_t,
+                  c10::optional<Tensor> lr_table,
+                  c10::optional<Tensor> lr_out, double lr, double mu,
+                  bool nesterov, bool zero_grad, Tensor chunks,
+                  Tensor seg_mul, c10::optional<Tensor> grad_bf16,
+                  double grad_scale, c10::optional<Tensor> probe_prev,
+                  c10::optional<Tensor> probe_sumsq,
+                  c10::optional<Tensor> probe_out) {
+  check_f32(master, "master");
+  check_probe(probe_prev, probe_sumsq, probe_out);
+  TORCH_CHECK(grad.numel() == master.numel()
+                  && (!mom.has_value() || mom->numel() == master.numel()),
+              "grad / mom must match master's size");
+  TORCH_CHECK(!nesterov || (mom.has_value() && mu > 0.0),
+              "nesterov needs a momentum buffer and momentum > 0");
+  SegTable t = seg_table(chunks, seg_mul, master);
+  long T = 0;
+  const float* table = sched_table(lr_table, master, &T);
+  TORCH_CHECK(table == nullptr || step_t.has_value(),
+              "lr_table needs the step_t device counter");
+  float* out = sched_scalar(lr_out, master, "lr_out");
+  float* st = sched_scalar(step_t, master, "step_t");
+  launch_sgd_step_seg(master.data_ptr<float>(), grad.data_ptr<float>(),
+                      opt_ptr<float>(mom), opt_ptr(shadow), (float)lr,
+                      (float)mu, zero_grad ? 1 : 0, opt_ptr(grad_bf16),
+                      (float)grad_scale, opt_ptr<float>(probe_prev),
+                      opt_ptr<float>(probe_sumsq), opt_ptr<float>(probe_out),
+                      st, table, T, out, nesterov ? 1 : 0, t.chunks,
+                      t.nchunks, t.seg_mul, cur_stream());
+}
+
 void permute_krsc_rsck(Tensor src, Tensor dst, Tensor meta,
                        int64_t max_elem) {
   TORCH_CHECK(meta.scalar_type() == torch::kInt32 && meta.is_cuda());
@@ -1229,6 +1371,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("wd"), py::arg("nesterov"), py::arg("zero_grad"),
         py::arg("grad_bf16") = py::none(), py::arg("grad_scale") = 1.0,
         py::arg("probe_prev") = py::none(),
+        py::arg("probe_sumsq") = py::none(),
+        py::arg("probe_out") = py::none());
+  m.def("seg_norms", &seg_norms, py::arg("master"), py::arg("grad"),
+        py::arg("chunks"), py::arg("seg_meta"), py::arg("partials"),
+        py::arg("seg_norms"), py::arg("seg_mul"), py::arg("norm_out"),
+        py::arg("wd"), py::arg("max_norm"), py::arg("lars"), py::arg("eta"),
+        py::arg("grad_bf16") = py::none(), py::arg("grad_scale") = 1.0);
+  m.def("adam_step_seg", &adam_step_seg, py::arg("master"), py::arg("grad"),
+        py::arg("m"), py::arg("v"), py::arg("shadow"), py::arg("step_t"),
+        py::arg("lr_table"), py::arg("lr_out"), py::arg("lr"), py::arg("b1"),
+        py::arg("b2"), py::arg("eps"), py::arg("decoupled"),
+        py::arg("zero_grad"), py::arg("chunks"), py::arg("seg_mul"),
+        py::arg("extra_zero") = py::none(), py::arg("grad_bf16") = py::none(),
+        py::arg("grad_scale") = 1.0, py::arg("probe_prev") = py::none(),
+        py::arg("probe_sumsq") = py::none(),
+        py::arg("probe_out") = py::none());
+  m.def("sgd_step_seg", &sgd_step_seg, py::arg("master"), py::arg("grad"),
+        py::arg("mom"), py::arg("shadow"), py::arg("step_t"),
+        py::arg("lr_table"), py::arg("lr_out"), py::arg("lr"), py::arg("mu"),
+        py::arg("nesterov"), py::arg("zero_grad"), py::arg("chunks"),
+        py::arg("seg_mul"), py::arg("grad_bf16") = py::none(),
+        py::arg("grad_scale") = 1.0, py::arg("probe_prev") = py::none(),
         py::arg("probe_sumsq") = py::none(),
         py::arg("probe_out") = py::none());
   m.def("permute_krsc_rsck", &permute_krsc_rsck);

@@ -1743,7 +1743,12 @@ __global__ __launch_bounds__(256) void k_ce_ls_fwd_bwd(
 // Nesterov) evaluate one update expression with one contraction.
 // DECOUPLED (AdamW): wd is not added to g; w is scaled by (1 − lr·wd) before
 // the Adam update, as torch.optim.AdamW does.
-template <bool DECOUPLED>
+// SEG (the *_seg kernels): `wd` is the segment's weight multiplier and the
+// gradient is first scaled by the segment's `gmul` (clip factor × LARS trust
+// ratio).  The scale is its own rounded product in front of the unchanged
+// expression, skipped when gmul == 1, so a uniform table reproduces the
+// unsegmented kernels bit for bit.
+template <bool DECOUPLED, bool SEG = false>
 __device__ __forceinline__ void adam_body(
     float* __restrict__ master, float* __restrict__ grad,
     float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ shadow,
@@ -1751,7 +1756,7 @@ __device__ __forceinline__ void adam_body(
     float eps, float wd, int zero_grad, float* __restrict__ extra_zero,
     long n_extra, const bf16* __restrict__ gsrc, float gscale,
     float* __restrict__ prev, float* __restrict__ sumsq, long i0,
-    long istride) {
+    long istride, float gmul = 1.f) {
   for (long i = i0; i < n_extra; i += istride) extra_zero[i] = 0.f;
   float t = step_t[0];
   float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
@@ -1764,6 +1769,7 @@ __device__ __forceinline__ void adam_body(
       prev[i] = gl;
       acc += d * d;
     }
+    if (SEG && gmul != 1.f) g *= gmul;
     float w = master[i];
     if (DECOUPLED) {
       if (wd != 0.f) w *= 1.f - lr * wd;
@@ -1790,13 +1796,13 @@ __device__ __forceinline__ void adam_body(
 }
 
 // NESTEROV: u = μ·mom + g; mom = u; w −= lr·(g + μ·u)  (torch's definition)
-template <bool NESTEROV>
+template <bool NESTEROV, bool SEG = false>
 __device__ __forceinline__ void sgd_body(
     float* __restrict__ master, float* __restrict__ grad,
     float* __restrict__ mom, bf16* __restrict__ shadow, long n, float lr,
     float mu, float wd, int zero_grad, const bf16* __restrict__ gsrc,
     float gscale, float* __restrict__ prev, float* __restrict__ sumsq,
-    long i0, long istride) {
+    long i0, long istride, float gmul = 1.f) {
   float acc = 0.f;
   for (long i = i0; i < n; i += istride) {
     float gl = grad[i];
@@ -1806,6 +1812,7 @@ __device__ __forceinline__ void sgd_body(
       prev[i] = gl;
       acc += d * d;
     }
+    if (SEG && gmul != 1.f) g *= gmul;
     float w = master[i];
     if (wd != 0.f) g += wd * w;
     float u = (mom != nullptr) ? (mu * mom[i] + g) : g;
@@ -1906,6 +1913,209 @@ __global__ __launch_bounds__(256) void k_sgd_step_ex(
 }
 
 __global__ void k_inc_step(float* step_t) { step_t[0] += 1.f; }
+
+// ---------------------------------------------- segmented optimizer step --
+// Segment s = one parameter = [b_s, b_{s+1}) of the flat buffer.  The host
+// cuts every segment into chunks of <= 4096 elements that never cross a
+// segment: chunks[c] = (segment, start, length).  One workgroup per chunk,
+// so the segment is workgroup-uniform in every kernel below (no per-element
+// search).  seg_meta[s] = (first chunk, one past the last chunk, flags) with
+// flags bit 0 = decay_s, bit 1 = adapt_s.
+// Contract (docs/KERNELS.md "Segmented step"): G_s = Σg², W_s = Σw²,
+// N = sqrt(Σ_s G_s), c = min(1, max_norm/(N + 1e-6)) (1 when max_norm <= 0),
+// wd_s = wd·decay_s, q_s = η·‖w‖/(c·‖g‖ + wd_s·‖w‖ + 1e-8) for LARS on an
+// adapt segment with ‖w‖ > 0 and ‖g‖ > 0, else 1;
+// seg_mul[s] = (gmul_s, wmul_s) = (q_s·c, q_s·wd_s).
+// No float atomics: partials are stored per chunk and folded in a fixed
+// order, so the result is bitwise reproducible and a replayed graph cannot
+// accumulate into stale state.
+template <int NW>  // waves per workgroup
+__device__ __forceinline__ float block_sum(float x, float* ws) {
+  x = wave_reduce_sum(x);
+  __syncthreads();  // ws may still be read from an earlier call
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = x;
+  __syncthreads();
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NW; i++) s += ws[i];
+  return s;
+}
+
+// partials[c] = (Σg², Σw²) of chunk c; g is the step kernel's effective
+// gradient (b2f(gsrc)·gscale, else grad).  Loads are 16-byte vectors over
+// the aligned middle of the chunk (float4; 8×bf16 + 2×float4 with gsrc),
+// scalar over its unaligned head and tail.  need_w = 0 (clip without LARS)
+// skips the master stream and stores Σw² = 0.
+__global__ __launch_bounds__(256) void k_seg_sumsq_partial(
+    const float* __restrict__ master, const float* __restrict__ grad,
+    const bf16* __restrict__ gsrc, float gscale,
+    const int* __restrict__ chunks, float* __restrict__ partials,
+    int need_w) {
+  __shared__ float ws[4];
+  const int c = blockIdx.x;
+  const long start = chunks[c * 3 + 1];
+  const int len = chunks[c * 3 + 2];
+  const int A = gsrc != nullptr ? 8 : 4;  // elements per vector step
+  int head = (int)((A - (start & (A - 1))) & (A - 1));
+  if (head > len) head = len;
+  const int nvec = (len - head) / A;
+  const long vbase = start + head;
+  const long tbase = vbase + (long)nvec * A;
+  const int tail = len - head - nvec * A;
+  float ag = 0.f, aw = 0.f;
+  // head and tail: at most 2·(A−1) scalars, one per thread
+  {
+    const int t = threadIdx.x;
+    long i = -1;
+    if (t < head) i = start + t;
+    else if (t - head < tail) i = tbase + (t - head);
+    if (i >= 0) {
+      float g = gsrc != nullptr ? b2f(gsrc[i]) * gscale : grad[i];
+      ag += g * g;
+      if (need_w) { float w = master[i]; aw += w * w; }
+    }
+  }
+  if (gsrc != nullptr) {
+    for (int k = threadIdx.x; k < nvec; k += 256) {
+      const long i = vbase + (long)k * 8;
+      const uint4 raw = *reinterpret_cast<const uint4*>(gsrc + i);
+      const unsigned r[4] = {raw.x, raw.y, raw.z, raw.w};
+#pragma unroll
+      for (int j = 0; j < 4; j++) {
+        float lo = __uint_as_float(r[j] << 16) * gscale;
+        float hi = __uint_as_float(r[j] & 0xffff0000u) * gscale;
+        ag += lo * lo;
+        ag += hi * hi;
+      }
+      if (need_w) {
+        const float4 w0 = *reinterpret_cast<const float4*>(master + i);
+        const float4 w1 = *reinterpret_cast<const float4*>(master + i + 4);
+        aw += w0.x * w0.x; aw += w0.y * w0.y;
+        aw += w0.z * w0.z; aw += w0.w * w0.w;
+        aw += w1.x * w1.x; aw += w1.y * w1.y;
+        aw += w1.z * w1.z; aw += w1.w * w1.w;
+      }
+    }
+  } else {
+    for (int k = threadIdx.x; k < nvec; k += 256) {
+      const long i = vbase + (long)k * 4;
+      const float4 g = *reinterpret_cast<const float4*>(grad + i);
+      ag += g.x * g.x; ag += g.y * g.y; ag += g.z * g.z; ag += g.w * g.w;
+      if (need_w) {
+        const float4 w = *reinterpret_cast<const float4*>(master + i);
+        aw += w.x * w.x; aw += w.y * w.y; aw += w.z * w.z; aw += w.w * w.w;
+      }
+    }
+  }
+  ag = block_sum<4>(ag, ws);
+  aw = block_sum<4>(aw, ws);
+  if (threadIdx.x == 0) {
+    partials[2 * c] = ag;
+    partials[2 * c + 1] = aw;
+  }
+}
+
+// ONE workgroup of 16 waves (the fold of one segment is a chain of dependent
+// latencies — table entry, partials, wave reduce — so segments per wave set
+// the time: 4 waves measured 15 us at ResNet18's 62 segments).  Wave w folds
+// segments w, w+16, ...: its 64 lanes sum the segment's chunk partials
+// strided, then a wave reduce — a fixed order.
+// seg_norms[s] = (G_s, W_s) is both the hand-over to the second phase and a
+// readable by-product.  Then N, c, q_s and seg_mul; norm_out = (N, c).
+constexpr int kSegFinWaves = 16;
+__global__ __launch_bounds__(64 * kSegFinWaves) void k_seg_finalize(
+    const float* __restrict__ partials, const int* __restrict__ seg_meta,
+    int nseg, float wd, float max_norm, int lars, float eta,
+    float* __restrict__ seg_norms, float* __restrict__ seg_mul,
+    float* __restrict__ norm_out) {
+  constexpr int NT = 64 * kSegFinWaves;
+  __shared__ float ws[kSegFinWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int s = wave; s < nseg; s += kSegFinWaves) {
+    const int c0 = seg_meta[s * 3], c1 = seg_meta[s * 3 + 1];
+    float ag = 0.f, aw = 0.f;
+    for (int c = c0 + lane; c < c1; c += 64) {
+      ag += partials[2 * c];
+      aw += partials[2 * c + 1];
+    }
+    ag = wave_reduce_sum(ag);
+    aw = wave_reduce_sum(aw);
+    if (lane == 0) {
+      seg_norms[2 * s] = ag;
+      seg_norms[2 * s + 1] = aw;
+    }
+  }
+  __threadfence_block();
+  __syncthreads();
+  float tot = 0.f;
+  for (int s = threadIdx.x; s < nseg; s += NT) tot += seg_norms[2 * s];
+  tot = block_sum<kSegFinWaves>(tot, ws);
+  const float N = sqrtf(tot);
+  float c = 1.f;
+  if (max_norm > 0.f) c = fminf(1.f, max_norm / (N + 1e-6f));
+  for (int s = threadIdx.x; s < nseg; s += NT) {
+    const int flags = seg_meta[s * 3 + 2];
+    const float wd_s = (flags & 1) ? wd : 0.f;
+    float q = 1.f;
+    if (lars && (flags & 2)) {
+      const float gn = c * sqrtf(seg_norms[2 * s]);
+      const float wn = sqrtf(seg_norms[2 * s + 1]);
+      if (wn > 0.f && gn > 0.f) q = eta * wn / (gn + wd_s * wn + 1e-8f);
+    }
+    seg_mul[2 * s] = q * c;
+    seg_mul[2 * s + 1] = q * wd_s;
+  }
+  if (threadIdx.x == 0) {
+    norm_out[0] = N;
+    norm_out[1] = c;
+  }
+}
+
+// The *_ex kernels with per-segment multipliers: grid = chunks, the body's
+// range is the chunk.  Every other duty (lr table / lr_out, shadow,
+// zero_grad, extra_zero, gsrc, probe) is the body's, unchanged.
+template <bool NESTEROV>
+__global__ __launch_bounds__(256) void k_sgd_step_seg(
+    float* __restrict__ master, float* __restrict__ grad,
+    float* __restrict__ mom, bf16* __restrict__ shadow, float lr, float mu,
+    int zero_grad, const bf16* __restrict__ gsrc, float gscale,
+    float* __restrict__ prev, float* __restrict__ sumsq,
+    const float* __restrict__ step_t, const float* __restrict__ lr_table,
+    long T, float* __restrict__ lr_out, const int* __restrict__ chunks,
+    const float* __restrict__ seg_mul) {
+  lr = sched_lr(step_t, lr_table, T, lr, lr_out);
+  const int c = blockIdx.x;
+  const int s = chunks[c * 3];
+  const long start = chunks[c * 3 + 1];
+  const long end = start + chunks[c * 3 + 2];
+  sgd_body<NESTEROV, true>(master, grad, mom, shadow, end, lr, mu,
+                           seg_mul[2 * s + 1], zero_grad, gsrc, gscale, prev,
+                           sumsq, start + threadIdx.x, 256, seg_mul[2 * s]);
+}
+
+template <bool DECOUPLED>
+__global__ __launch_bounds__(256) void k_adam_step_seg(
+    float* __restrict__ master, float* __restrict__ grad,
+    float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ shadow,
+    const float* __restrict__ step_t, float lr, float b1, float b2,
+    float eps, int zero_grad, float* __restrict__ extra_zero, long n_extra,
+    const bf16* __restrict__ gsrc, float gscale, float* __restrict__ prev,
+    float* __restrict__ sumsq, const float* __restrict__ lr_table, long T,
+    float* __restrict__ lr_out, const int* __restrict__ chunks,
+    const float* __restrict__ seg_mul) {
+  lr = sched_lr(step_t, lr_table, T, lr, lr_out);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_extra;
+       i += (long)gridDim.x * 256)
+    extra_zero[i] = 0.f;
+  const int c = blockIdx.x;
+  const int s = chunks[c * 3];
+  const long start = chunks[c * 3 + 1];
+  const long end = start + chunks[c * 3 + 2];
+  adam_body<DECOUPLED, true>(master, grad, m, v, shadow, step_t, end, lr, b1,
+                             b2, eps, seg_mul[2 * s + 1], zero_grad, nullptr,
+                             0, gsrc, gscale, prev, sumsq,
+                             start + threadIdx.x, 256, seg_mul[2 * s]);
+}
 
 // ------------------------------------------------ dgrad weight transpose ---
 // Batched KRSC -> RSCK permute of every conv weight shadow (one launch per
@@ -2690,6 +2900,56 @@ void launch_sgd_step_ex(float* master, float* grad, float* mom, void* shadow,
 #define LS(N) k_sgd_step_ex<N><<<gsz(n), 256, 0, st>>>( \
     master, grad, mom, (bf16*)shadow, n, lr, mu, wd, zero_grad, \
     (const bf16*)gsrc, gscale, prev, sumsq, step_t, lr_table, T, lr_out)
+  if (nesterov) LS(true); else LS(false);
+#undef LS
+  if (prev != nullptr)
+    k_gdiv_finalize<<<1, 1, 0, st>>>(sumsq, divout, 0);
+}
+
+// Segmented forms: the counter bumps are those of the *_ex launchers.
+void launch_seg_norms(const float* master, const float* grad,
+                      const void* gsrc, float gscale, const int* chunks,
+                      int nchunks, const int* seg_meta, int nseg,
+                      float* partials, float* seg_norms, float* seg_mul,
+                      float* norm_out, float wd, float max_norm, int lars,
+                      float eta, hipStream_t st) {
+  k_seg_sumsq_partial<<<nchunks, 256, 0, st>>>(master, grad,
+                                               (const bf16*)gsrc, gscale,
+                                               chunks, partials, lars);
+  k_seg_finalize<<<1, 64 * kSegFinWaves, 0, st>>>(partials, seg_meta, nseg, wd, max_norm,
+                                    lars, eta, seg_norms, seg_mul, norm_out);
+}
+
+void launch_adam_step_seg(float* master, float* grad, float* m, float* v,
+                          void* shadow, float* step_t, float lr, float b1,
+                          float b2, float eps, int zero_grad,
+                          float* extra_zero, long n_extra, const void* gsrc,
+                          float gscale, float* prev, float* sumsq,
+                          float* divout, const float* lr_table, long T,
+                          float* lr_out, int decoupled, const int* chunks,
+                          int nchunks, const float* seg_mul, hipStream_t st) {
+  k_inc_step<<<1, 1, 0, st>>>(step_t);
+#define LA(D) k_adam_step_seg<D><<<nchunks, 256, 0, st>>>( \
+    master, grad, m, v, (bf16*)shadow, step_t, lr, b1, b2, eps, zero_grad, \
+    extra_zero, n_extra, (const bf16*)gsrc, gscale, prev, sumsq, lr_table, \
+    T, lr_out, chunks, seg_mul)
+  if (decoupled) LA(true); else LA(false);
+#undef LA
+  if (prev != nullptr)
+    k_gdiv_finalize<<<1, 1, 0, st>>>(sumsq, divout, 0);
+}
+
+void launch_sgd_step_seg(float* master, float* grad, float* mom, void* shadow,
+                         float lr, float mu, int zero_grad, const void* gsrc,
+                         float gscale, float* prev, float* sumsq,
+                         float* divout, float* step_t, const float* lr_table,
+                         long T, float* lr_out, int nesterov,
+                         const int* chunks, int nchunks, const float* seg_mul,
+                         hipStream_t st) {
+  if (lr_table != nullptr) k_inc_step<<<1, 1, 0, st>>>(step_t);
+#define LS(N) k_sgd_step_seg<N><<<nchunks, 256, 0, st>>>( \
+    master, grad, mom, (bf16*)shadow, lr, mu, zero_grad, (const bf16*)gsrc, \
+    gscale, prev, sumsq, step_t, lr_table, T, lr_out, chunks, seg_mul)
   if (nesterov) LS(true); else LS(false);
 #undef LS
   if (prev != nullptr)

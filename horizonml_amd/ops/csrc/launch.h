@@ -256,6 +256,31 @@ void launch_sgd_step_ex(float* master, float* grad, float* mom, void* shadow,
                         float* sumsq, float* divout, float* step_t,
                         const float* lr_table, long T, float* lr_out,
                         int nesterov, hipStream_t st);
+// Segmented forms: chunks int32 [nchunks][3] = (segment, start, length),
+// seg_meta int32 [nseg][3] = (chunk begin, chunk end, flags), seg_mul f32
+// [nseg][2] = (gmul, wmul).  launch_seg_norms is the two-dispatch norm
+// reduction (partials, finalize) that fills seg_mul and norm_out = (N, c).
+void launch_seg_norms(const float* master, const float* grad,
+                      const void* gsrc, float gscale, const int* chunks,
+                      int nchunks, const int* seg_meta, int nseg,
+                      float* partials, float* seg_norms, float* seg_mul,
+                      float* norm_out, float wd, float max_norm, int lars,
+                      float eta, hipStream_t st);
+void launch_adam_step_seg(float* master, float* grad, float* m, float* v,
+                          void* shadow, float* step_t, float lr, float b1,
+                          float b2, float eps, int zero_grad,
+                          float* extra_zero, long n_extra, const void* gsrc,
+                          float gscale, float* prev, float* sumsq,
+                          float* divout, const float* lr_table, long T,
+                          float* lr_out, int decoupled, const int* chunks,
+                          int nchunks, const float* seg_mul, hipStream_t st);
+void launch_sgd_step_seg(float* master, float* grad, float* mom, void* shadow,
+                         float lr, float mu, int zero_grad, const void* gsrc,
+                         float gscale, float* prev, float* sumsq,
+                         float* divout, float* step_t, const float* lr_table,
+                         long T, float* lr_out, int nesterov,
+                         const int* chunks, int nchunks, const float* seg_mul,
+                         hipStream_t st);
 
 // elem_kernels.hip: layout, probes, input pipeline
 void launch_permute_krsc_rsck(const void* src, void* dst, const int* meta,

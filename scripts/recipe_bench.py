@@ -35,6 +35,17 @@ CONFIGS = {
                             lr_schedule="cosine", warmup_epochs=1,
                             nesterov=True, weight_decay=5e-4,
                             label_smoothing=0.1),
+    # segmented step: static table only (0 added dispatches) ...
+    "sgd_nodecay": dict(optimizer_name="sgd", lr=0.1, weight_decay=5e-4,
+                        no_decay_1d=True),
+    # ... and with the per-step norm reduction (2 added dispatches)
+    "sgd_clip": dict(optimizer_name="sgd", lr=0.1, clip_grad_norm=5.0),
+    "sgd_lars_full": dict(optimizer_name="sgd", lr=0.1,
+                          lr_schedule="cosine", warmup_epochs=1,
+                          nesterov=True, weight_decay=5e-4,
+                          label_smoothing=0.1, lars=True, clip_grad_norm=5.0,
+                          no_decay_1d=True),
+    "adam_clip": dict(optimizer_name="adam", lr=1e-3, clip_grad_norm=1.0),
 }
 
 
