@@ -59,6 +59,34 @@ bool g_wgrad_tr = env_long("HZ_WGRAD_TR", 1) != 0;
 void set_wgrad_tr(bool on) { g_wgrad_tr = on; }
 bool wgrad_tr_enabled() { return g_wgrad_tr; }
 
+// Tap window (launch.h, clip_taps): forward, dgrad and wgrad skip the filter
+// taps that only ever meet padding.  HZ_TAP_CLIP (read at load, default on);
+// off = every conv walks its whole filter, kept for A/B timing and as the
+// tests' reference.  Consulted in one place, make_convp.
+bool g_tap_clip = env_long("HZ_TAP_CLIP", 1) != 0;
+void set_tap_clip(bool on) { g_tap_clip = on; }
+bool tap_clip_enabled() { return g_tap_clip; }
+
+// (r0, s0, R', S') of a conv's tap window, whatever the switch says.
+std::vector<int64_t> conv_tap_window(int64_t H, int64_t W, int64_t R,
+                                     int64_t S, int64_t stride, int64_t pad) {
+  TORCH_CHECK(stride >= 1 && pad >= 0 && R >= 1 && S >= 1 &&
+                  H + 2 * pad >= R && W + 2 * pad >= S,
+              "conv_tap_window: empty output or bad geometry");
+  ConvP p{};
+  p.H = (int)H;
+  p.W = (int)W;
+  p.C = 1;
+  p.R = p.Rf = (int)R;
+  p.S = p.Sf = (int)S;
+  p.str = (int)stride;
+  p.pad = (int)pad;
+  p.Ho = (p.H + 2 * p.pad - p.R) / p.str + 1;
+  p.Wo = (p.W + 2 * p.pad - p.S) / p.str + 1;
+  p = clip_taps(p);
+  return {p.r0, p.s0, p.R, p.S};
+}
+
 // ---- deferred (batched) wgrad ---------------------------------------------
 // The weight-gradient GEMMs are off the backward's critical chain (nothing
 // reads dW until the optimizer step), and each conv's own wgrad underfills
@@ -177,6 +205,9 @@ void flush_one_group(int group_lo, int group_hi) {
     // swept on MI355X: M=2048 admits CIFAR-bs64 layer1 (M=4096) and
     // costs ~2% at the parity point; 5000 keeps r50@224 at 9.39 ms
     static const int m_min = (int)env_long("HZ_WG_TK3_M", 5000);
+    // a clipped task (tap window) stays in the 64-wide classes, the only
+    // ones whose kernels carry the window form of wgrad_tile
+    if (taps_clipped(p)) return 64;
     return (p.Kd >= kd_min && p.M >= m_min) ? 128 : 64;
   };
   auto tko_of = [](const ConvP& p) {
@@ -233,6 +264,7 @@ void flush_one_group(int group_lo, int group_hi) {
     t.ws = ws_base + ws_off[i];
     t.dW = pend[i].dw.data_ptr<float>();
     t.n = (long)pend[i].p.K * pend[i].p.Kd;
+    wred_set_window(&t, pend[i].p);
     t.msplit = msplit[i];
     t.base = rblocks;
     rblocks += cdiv_i(t.n, 1024);
@@ -279,22 +311,30 @@ Tensor empty_cl_bf16(int64_t n, int64_t c, int64_t h, int64_t w,
                    at::MemoryFormat::ChannelsLast);
 }
 
-ConvP make_convp(const Tensor& x, int K, int R, int S, int stride, int pad) {
+// Forward geometry of one conv, clipped to its tap window when the switch is
+// on: the one place every conv entry point gets its ConvP from.
+ConvP make_convp(int Nb, int C, int H, int W, int K, int R, int S, int stride,
+                 int pad) {
   ConvP p{};
-  p.Nb = (int)x.size(0);
-  p.C = (int)x.size(1);
-  p.H = (int)x.size(2);
-  p.W = (int)x.size(3);
+  p.Nb = Nb;
+  p.C = C;
+  p.H = H;
+  p.W = W;
   p.K = K;
-  p.R = R;
-  p.S = S;
+  p.R = p.Rf = R;
+  p.S = p.Sf = S;
   p.str = stride;
   p.pad = pad;
   p.Ho = (p.H + 2 * pad - R) / stride + 1;
   p.Wo = (p.W + 2 * pad - S) / stride + 1;
   p.M = p.Nb * p.Ho * p.Wo;
   p.Kd = R * S * p.C;
-  return p;
+  return g_tap_clip ? clip_taps(p) : p;
+}
+
+ConvP make_convp(const Tensor& x, int K, int R, int S, int stride, int pad) {
+  return make_convp((int)x.size(0), (int)x.size(1), (int)x.size(2),
+                    (int)x.size(3), K, R, S, stride, pad);
 }
 
 // ---------------------------------------------------------------- conv+BN --
@@ -410,7 +450,7 @@ Tensor dgrad_dx(const Tensor& dconv, const Tensor& w,
   TORCH_CHECK(wt.is_contiguous() && wt.scalar_type() == torch::kBFloat16,
               krsc ? "w must be contiguous bf16"
                    : "w_rsck must be contiguous bf16");
-  TORCH_CHECK(wt.numel() == (int64_t)p.K * p.R * p.S * p.C,
+  TORCH_CHECK(wt.numel() == (int64_t)p.K * p.Rf * p.Sf * p.C,
               "dgrad weight has ", wt.numel(), " elements, expected K*R*S*C");
   auto fopt = dconv.options().dtype(torch::kFloat32);
   const int layout = krsc ? DGRAD_W_KRSC : DGRAD_W_RSCK;
@@ -470,20 +510,9 @@ Tensor conv_dgrad_only(Tensor dz, Tensor w, int64_t H, int64_t W,
   check_cl(dz, "dz");
   TORCH_CHECK(w.dim() == 4 && w.size(0) == dz.size(1),
               "w must be [K,R,S,C] with K = dz channels");
-  ConvP p{};
-  p.Nb = (int)dz.size(0);
-  p.C = (int)w.size(3);
-  p.H = (int)H;
-  p.W = (int)W;
-  p.K = (int)w.size(0);
-  p.R = (int)w.size(1);
-  p.S = (int)w.size(2);
-  p.str = (int)stride;
-  p.pad = (int)pad;
-  p.Ho = (p.H + 2 * p.pad - p.R) / p.str + 1;
-  p.Wo = (p.W + 2 * p.pad - p.S) / p.str + 1;
-  p.M = p.Nb * p.Ho * p.Wo;
-  p.Kd = p.R * p.S * p.C;
+  const ConvP p = make_convp((int)dz.size(0), (int)w.size(3), (int)H, (int)W,
+                             (int)w.size(0), (int)w.size(1), (int)w.size(2),
+                             (int)stride, (int)pad);
   TORCH_CHECK(dz.size(2) == p.Ho && dz.size(3) == p.Wo,
               "dz spatial size does not match H, W, stride, pad");
   if (dx_accum.has_value()) {
@@ -1420,4 +1449,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dgrad_krsc_enabled", &dgrad_krsc_enabled);
   m.def("set_wgrad_tr", &set_wgrad_tr);
   m.def("wgrad_tr_enabled", &wgrad_tr_enabled);
+  m.def("set_tap_clip", &set_tap_clip);
+  m.def("tap_clip_enabled", &tap_clip_enabled);
+  m.def("conv_tap_window", &conv_tap_window);
 }

@@ -29,7 +29,15 @@
 #include "common.h"  // ConvP, MagicP and make_magic come from launch.h
 
 // ---------------------------------------------------------------- staging --
-template <int MODE>
+// Tap window (launch.h, clip_taps): R, S, Kd are the window's and the k index
+// runs over the window.  CLIP is a template flag of every gather and of the
+// kernels built on them: CLIP = false is the whole-filter address arithmetic
+// (no origin, Rf = R, Sf = S) and compiles to what it compiled to before the
+// window existed; CLIP = true adds the origin (r0, s0) to the patch
+// coordinates and addresses weights / dW through the full Rf×Sf filter.  The
+// host picks the flag per conv (taps_clipped), and instantiates CLIP = true
+// for the 64-wide latency tiles only: a clipped conv has a 1-2 pixel map.
+template <int MODE, bool CLIP = false>
 DEV int a_addr(const ConvP& p, const MagicP& mg, int m, int k, bool& valid) {
   if (MODE == 0) {
     valid = (m < p.M) & (k < p.Kd);
@@ -41,8 +49,10 @@ DEV int a_addr(const ConvP& p, const MagicP& mg, int m, int k, bool& valid) {
     unsigned ho = fdiv(hw, mg, 1), wo = fmod(hw, ho, mg, 1);
     unsigned r = fdiv(k, mg, 2), rm = fmod(k, r, mg, 2);
     unsigned sx = fdiv(rm, mg, 3), c = fmod(rm, sx, mg, 3);
-    int hi = (int)ho * p.str - p.pad + (int)r;
-    int wi = (int)wo * p.str - p.pad + (int)sx;
+    const int ph = CLIP ? p.pad - p.r0 : p.pad;
+    const int pw = CLIP ? p.pad - p.s0 : p.pad;
+    int hi = (int)ho * p.str - ph + (int)r;
+    int wi = (int)wo * p.str - pw + (int)sx;
     valid = (m < p.M) & (k < p.Kd) & (hi >= 0) & (hi < p.H) & (wi >= 0) & (wi < p.W);
     return (((int)n * p.H + hi) * p.W + wi) * p.C + (int)c;
   } else {
@@ -51,7 +61,9 @@ DEV int a_addr(const ConvP& p, const MagicP& mg, int m, int k, bool& valid) {
     unsigned hi = fdiv(hw, mg, 1), wi = fmod(hw, hi, mg, 1);
     unsigned r = fdiv(k, mg, 2), rm = fmod(k, r, mg, 2);
     unsigned sx = fdiv(rm, mg, 3), ko = fmod(rm, sx, mg, 3);
-    int hs = (int)hi + p.pad - (int)r, ws = (int)wi + p.pad - (int)sx;
+    const int ph = CLIP ? p.pad - p.r0 : p.pad;
+    const int pw = CLIP ? p.pad - p.s0 : p.pad;
+    int hs = (int)hi + ph - (int)r, ws = (int)wi + pw - (int)sx;
     bool ok = (m < p.M) & (k < p.Kd) & (hs >= 0) & (ws >= 0) &&
               (hs % p.str == 0) && (ws % p.str == 0);
     int ho = hs / p.str, wo = ws / p.str;  // str is 1 or 2: cheap
@@ -61,26 +73,40 @@ DEV int a_addr(const ConvP& p, const MagicP& mg, int m, int k, bool& valid) {
   }
 }
 
-template <int MODE>
+// window tap index rs = r*S + s at reduction index k (slot 2 = S * channels)
+// -> tap (r0 + r)*Sf + s0 + s of the filter as stored
+DEV int full_tap(const ConvP& p, const MagicP& mg, int k, int rs) {
+  int r = (int)fdiv(k, mg, 2);
+  return (p.r0 + r) * p.Sf + p.s0 + (rs - r * p.S);
+}
+
+template <int MODE, bool CLIP = false>
 DEV int b_addr(const ConvP& p, const MagicP& mg, int n, int k, int Ntot,
                bool& valid) {
   if (MODE == 2) {
     // W_rsck[(r*S+s)*C + c][ko] with k = (r*S+s)*K + ko, n = c
     unsigned rs = fdiv(k, mg, 3), ko = fmod(k, rs, mg, 3);
     valid = (n < Ntot) & (k < p.Kd);
+    if (CLIP) rs = (unsigned)full_tap(p, mg, k, (int)rs);
     return ((int)rs * p.C + n) * p.K + (int)ko;
   }
   valid = (n < Ntot) & (k < p.Kd);
+  if (MODE == 1 && CLIP) {
+    // W[n][r0+r][s0+s][c]: window row r sits (Sf - S)*C further on per row
+    unsigned r = fdiv(k, mg, 2);
+    return n * (p.Rf * p.Sf * p.C) +
+           (p.r0 * p.Sf + p.s0 + (int)r * (p.Sf - p.S)) * p.C + k;
+  }
   return n * p.Kd + k;
 }
 
-template <int MODE, bool VEC>
+template <int MODE, bool VEC, bool CLIP = false>
 DEV V8 load8_a(const bf16* __restrict__ src, const ConvP& p,
                const MagicP& mg, int m, int k) {
   V8 v;
   if (VEC) {
     bool ok;
-    int a = a_addr<MODE>(p, mg, m, k, ok);
+    int a = a_addr<MODE, CLIP>(p, mg, m, k, ok);
     if (ok) v.u = *(const uint4*)(src + a);
     else v.u = uint4{0, 0, 0, 0};
   } else if (MODE == 1) {
@@ -92,7 +118,8 @@ DEV V8 load8_a(const bf16* __restrict__ src, const ConvP& p,
     int ho = hw / p.Wo, wo = hw % p.Wo;
     int r = k / (p.S * p.C), rm = k % (p.S * p.C);
     int s = rm / p.C, c = rm % p.C;
-    int hi = ho * p.str - p.pad + r, wi = wo * p.str - p.pad + s;
+    int hi = ho * p.str - (CLIP ? p.pad - p.r0 : p.pad) + r;
+    int wi = wo * p.str - (CLIP ? p.pad - p.s0 : p.pad) + s;
     const bool mok = m < p.M;
     int kk = k;
 #pragma unroll
@@ -115,26 +142,26 @@ DEV V8 load8_a(const bf16* __restrict__ src, const ConvP& p,
   } else {
     for (int e = 0; e < 8; e++) {
       bool ok;
-      int a = a_addr<MODE>(p, mg, m, k + e, ok);
+      int a = a_addr<MODE, CLIP>(p, mg, m, k + e, ok);
       v.e[e] = ok ? src[a] : (bf16)0.f;
     }
   }
   return v;
 }
 
-template <int MODE, bool VEC>
+template <int MODE, bool VEC, bool CLIP = false>
 DEV V8 load8_b(const bf16* __restrict__ src, const ConvP& p,
                const MagicP& mg, int n, int k, int Ntot) {
   V8 v;
   if (VEC) {
     bool ok;
-    int a = b_addr<MODE>(p, mg, n, k, Ntot, ok);
+    int a = b_addr<MODE, CLIP>(p, mg, n, k, Ntot, ok);
     if (ok) v.u = *(const uint4*)(src + a);
     else v.u = uint4{0, 0, 0, 0};
   } else {
     for (int e = 0; e < 8; e++) {
       bool ok;
-      int a = b_addr<MODE>(p, mg, n, k + e, Ntot, ok);
+      int a = b_addr<MODE, CLIP>(p, mg, n, k + e, Ntot, ok);
       v.e[e] = ok ? src[a] : (bf16)0.f;
     }
   }
@@ -173,13 +200,15 @@ DEV int lds_tr_off(int k, int n) {
 
 // One vec8 along c of k row `k`: W[ko][r][s][n .. n+7], (rs, ko) from one
 // fdiv/fmod.  Rows past kend and columns past C are zero-filled.
-template <bool VEC>
+template <bool VEC, bool CLIP = false>
 DEV V8 load8_b_krsc(const bf16* __restrict__ src, const ConvP& p,
                     const MagicP& mg, int n, int k, int kend, int Ntot) {
   V8 v;
   unsigned rs = fdiv(k, mg, 3), ko = fmod(k, rs, mg, 3);
   const bool kok = k < kend;
-  const int a = ((int)ko * p.R * p.S + (int)rs) * p.C + n;
+  const int a =
+      CLIP ? ((int)ko * p.Rf * p.Sf + full_tap(p, mg, k, (int)rs)) * p.C + n
+           : ((int)ko * p.R * p.S + (int)rs) * p.C + n;
   if (VEC) {
     if (kok && n < Ntot) v.u = *(const uint4*)(src + a);
     else v.u = uint4{0, 0, 0, 0};
@@ -221,7 +250,7 @@ DEV bf16x4 lds_read_tr16(const bf16* sp) {
 // from transposed reads.  The A side, the accumulators, the K order and the
 // epilogue are shared with the RSCK form.
 template <int MODE, bool VECA, bool VECB, bool STATS, bool SPLIT,
-          int TM = 64, int TN = 64, bool KRSC = false>
+          int TM = 64, int TN = 64, bool KRSC = false, bool CLIP = false>
 __global__ __launch_bounds__(256) void k_conv_mfma(
     const bf16* __restrict__ A, const bf16* __restrict__ Bw,
     bf16* __restrict__ Y, float* __restrict__ ws_out,
@@ -257,10 +286,10 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
   // B tile k-origin `kt`, chunk j -> registers; registers -> LDS buffer b
   auto load_b = [&](int j, int kt) -> V8 {
     if (KRSC)
-      return load8_b_krsc<VECB>(Bw, p, mg, n0 + bncol,
-                                kt + j * BKSTEP + bkrow, kend, Ntot);
-    return load8_b<MODE, VECB>(Bw, p, mg, n0 + j * 64 + srow, kt + scol,
-                               Ntot);
+      return load8_b_krsc<VECB, CLIP>(Bw, p, mg, n0 + bncol,
+                                      kt + j * BKSTEP + bkrow, kend, Ntot);
+    return load8_b<MODE, VECB, CLIP>(Bw, p, mg, n0 + j * 64 + srow,
+                                     kt + scol, Ntot);
   };
   auto store_b = [&](int b, int j, const V8& v) {
     if (KRSC)
@@ -281,7 +310,8 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
   // prologue: tile 0 -> LDS[0]; tile 1 -> registers
 #pragma unroll
   for (int j = 0; j < AC; j++) {
-    V8 a0 = load8_a<MODE, VECA>(A, p, mg, m0 + j * 64 + srow, kbeg + scol);
+    V8 a0 = load8_a<MODE, VECA, CLIP>(A, p, mg, m0 + j * 64 + srow,
+                                      kbeg + scol);
     *(V8*)&As[0][(j * 64 + srow) * LDA + scol] = a0;
   }
 #pragma unroll
@@ -290,8 +320,8 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
   if (kbeg + 32 < kend) {
 #pragma unroll
     for (int j = 0; j < AC; j++)
-      a_nx[j] = load8_a<MODE, VECA>(A, p, mg, m0 + j * 64 + srow,
-                                    kbeg + 32 + scol);
+      a_nx[j] = load8_a<MODE, VECA, CLIP>(A, p, mg, m0 + j * 64 + srow,
+                                          kbeg + 32 + scol);
 #pragma unroll
     for (int j = 0; j < BC; j++) b_nx[j] = load_b(j, kbeg + 32);
   }
@@ -310,8 +340,8 @@ __global__ __launch_bounds__(256) void k_conv_mfma(
       if (k0 + 64 < kend) {
 #pragma unroll
         for (int j = 0; j < AC; j++)
-          a_nx[j] = load8_a<MODE, VECA>(A, p, mg, m0 + j * 64 + srow,
-                                        k0 + 64 + scol);
+          a_nx[j] = load8_a<MODE, VECA, CLIP>(A, p, mg, m0 + j * 64 + srow,
+                                              k0 + 64 + scol);
 #pragma unroll
         for (int j = 0; j < BC; j++) b_nx[j] = load_b(j, k0 + 64);
       }
@@ -451,7 +481,7 @@ union WgradSmemT {
 using WgradSmem = WgradSmemT<64, 64>;
 
 // m-loop of the row-major form: accumulates rows [mbeg, mend) into acc.
-template <bool VECA, int TK3, int TKO>
+template <bool VECA, int TK3, int TKO, bool CLIP>
 DEV void wgrad_mloop_tr(const bf16* __restrict__ X,
                         const bf16* __restrict__ Dz, const ConvP& p,
                         const MagicP& mg, int Ntot, int k3_0, int n0,
@@ -470,7 +500,8 @@ DEV void wgrad_mloop_tr(const bf16* __restrict__ X,
   auto load_tile = [&](int mt) {
 #pragma unroll
     for (int j = 0; j < AC; j++)
-      a_nx[j] = load8_a<1, VECA>(X, p, mg, mt + sm, k3_0 + j * 64 + sv);
+      a_nx[j] =
+          load8_a<1, VECA, CLIP>(X, p, mg, mt + sm, k3_0 + j * 64 + sv);
 #pragma unroll
     for (int j = 0; j < DC; j++) {
       int m = mt + sm, n = n0 + j * 64 + sv;
@@ -529,7 +560,8 @@ DEV void wgrad_mloop_tr(const bf16* __restrict__ X,
   }
 }
 
-template <bool VECA, int TK3 = 64, int TKO = 64, bool TR = false>
+template <bool VECA, int TK3 = 64, int TKO = 64, bool TR = false,
+          bool CLIP = false>
 DEV void wgrad_tile(const bf16* __restrict__ X, const bf16* __restrict__ Dz,
                     float* __restrict__ out, const ConvP& p,
                     const MagicP& mg, int Ntot, int mchunk, int tx, int ty,
@@ -552,14 +584,15 @@ DEV void wgrad_tile(const bf16* __restrict__ X, const bf16* __restrict__ Dz,
   f32x4 acc[MI][NI] = {};
 
   if (TR) {
-    wgrad_mloop_tr<VECA, TK3, TKO>(X, Dz, p, mg, Ntot, k3_0, n0, mbeg, mend,
-                                   smem, acc);
+    wgrad_mloop_tr<VECA, TK3, TKO, CLIP>(X, Dz, p, mg, Ntot, k3_0, n0, mbeg,
+                                         mend, smem, acc);
   } else {
   // transposed-scatter m-loop, unchanged
   V8 a_nx[AC], d_nx[DC];
 #pragma unroll
   for (int j = 0; j < AC; j++)
-    a_nx[j] = load8_a<1, VECA>(X, p, mg, mbeg + sm, k3_0 + j * 64 + sv);
+    a_nx[j] =
+        load8_a<1, VECA, CLIP>(X, p, mg, mbeg + sm, k3_0 + j * 64 + sv);
 #pragma unroll
   for (int j = 0; j < DC; j++) {
     int m = mbeg + sm, n = n0 + j * 64 + sv;
@@ -592,8 +625,8 @@ DEV void wgrad_tile(const bf16* __restrict__ X, const bf16* __restrict__ Dz,
     if (m0 + 32 < mend) {
 #pragma unroll
       for (int j = 0; j < AC; j++)
-        a_nx[j] = load8_a<1, VECA>(X, p, mg, m0 + 32 + sm,
-                                   k3_0 + j * 64 + sv);
+        a_nx[j] = load8_a<1, VECA, CLIP>(X, p, mg, m0 + 32 + sm,
+                                         k3_0 + j * 64 + sv);
 #pragma unroll
       for (int j = 0; j < DC; j++) {
         int m = m0 + 32 + sm, n = n0 + j * 64 + sv;
@@ -646,7 +679,33 @@ DEV void wgrad_tile(const bf16* __restrict__ X, const bf16* __restrict__ Dz,
     }
     __syncthreads();
     const int gko = n0 + pass * 64 + ko_r;
-    if (gko < Ntot) {
+    if (CLIP && !split) {
+      // clipped task writing dW itself: row gko at the full-filter pitch,
+      // the k3 run mapped to its taps; dead taps are neither read nor
+      // written.  With C % 4 == 0 a float4 never straddles a tap.
+      if (gko < Ntot) {
+        const long row = (long)gko * (p.Rf * p.Sf * p.C) +
+                         (p.r0 * p.Sf + p.s0) * p.C;
+        const int skip = (p.Sf - p.S) * p.C;
+        if ((p.C & 3) == 0 && k3_0 + cch + CCH <= p.Kd) {
+#pragma unroll
+          for (int e = 0; e < CCH; e += 4) {
+            const int k3 = k3_0 + cch + e;
+            float* d4 = &dst[row + k3 + (int)fdiv(k3, mg, 2) * skip];
+            float4 v = *(const float4*)&smem.out[ko_r][cch + e];
+            float4 d = *(const float4*)d4;
+            v.x += d.x; v.y += d.y; v.z += d.z; v.w += d.w;
+            *(float4*)d4 = v;
+          }
+        } else {
+          for (int e = 0; e < CCH && k3_0 + cch + e < p.Kd; e++) {
+            const int k3 = k3_0 + cch + e;
+            dst[row + k3 + (int)fdiv(k3, mg, 2) * skip] +=
+                smem.out[ko_r][cch + e];
+          }
+        }
+      }
+    } else if (gko < Ntot) {
       long base = (long)gko * p.Kd + k3_0 + cch;
       if (k3_0 + cch + CCH <= p.Kd) {
 #pragma unroll
@@ -667,19 +726,59 @@ DEV void wgrad_tile(const bf16* __restrict__ X, const bf16* __restrict__ Dz,
   }
 }
 
-template <bool VECA, bool TR>
+template <bool VECA, bool TR, bool CLIP>
 __global__ __launch_bounds__(256) void k_wgrad(
     const bf16* __restrict__ X, const bf16* __restrict__ Dz,
     float* __restrict__ dW, ConvP p, MagicP mg, int Ntot, int mchunk) {
   __shared__ WgradSmem smem;
-  wgrad_tile<VECA, 64, 64, TR>(X, Dz, dW, p, mg, Ntot, mchunk, blockIdx.x,
-                               blockIdx.y, blockIdx.z, gridDim.z > 1, smem);
+  wgrad_tile<VECA, 64, 64, TR, CLIP>(X, Dz, dW, p, mg, Ntot, mchunk,
+                                     blockIdx.x, blockIdx.y, blockIdx.z,
+                                     gridDim.z > 1, smem);
+}
+
+// Slab reduce of a clipped task (WredTask::Kd > 0, launch.h): the slabs are
+// dense over the tap window, dW is the full filter.  Sums slab elements
+// [begin, end) and adds them into their taps; thread `tid` of `nthr`.
+DEV long wred_dst(const WredTask& t, unsigned i) {
+  unsigned ko = i / (unsigned)t.Kd, k3 = i - ko * (unsigned)t.Kd;
+  return (long)ko * t.KdF + t.org + k3 + (k3 / (unsigned)t.SC) * t.skip;
+}
+
+DEV void wred_scatter(const WredTask& t, long begin, long end, long tid,
+                      long nthr) {
+  // every term a multiple of 4 (C % 4 == 0): a float4 stays inside one tap
+  if (((t.Kd | t.SC | t.KdF | t.org | t.skip) & 3) == 0) {
+    for (long i4 = begin + tid * 4; i4 < end; i4 += nthr * 4) {
+      float4 v = *(const float4*)&t.ws[i4];
+      for (int z = 1; z < t.msplit; z++) {
+        float4 w = *(const float4*)&t.ws[(long)z * t.n + i4];
+        v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
+      }
+      float4* dp = (float4*)&t.dW[wred_dst(t, (unsigned)i4)];
+      float4 d = *dp;
+      d.x += v.x; d.y += v.y; d.z += v.z; d.w += v.w;
+      *dp = d;
+    }
+  } else {
+    for (long i = begin + tid; i < end; i += nthr) {
+      float v = t.ws[i];
+      for (int z = 1; z < t.msplit; z++) v += t.ws[(long)z * t.n + i];
+      t.dW[wred_dst(t, (unsigned)i)] += v;
+    }
+  }
 }
 
 // Σ over msplit wgrad slabs [z][n] -> dW[n] (+=; dW pre-zeroed or fresh).
-__global__ __launch_bounds__(256) void k_wgrad_reduce(
-    const float* __restrict__ ws, float* __restrict__ dW, long n,
-    int msplit) {
+__global__ __launch_bounds__(256) void k_wgrad_reduce(WredTask t) {
+  if (t.Kd > 0) {  // block-uniform
+    wred_scatter(t, 0, t.n, (long)blockIdx.x * blockDim.x + threadIdx.x,
+                 (long)gridDim.x * blockDim.x);
+    return;
+  }
+  const float* __restrict__ ws = t.ws;
+  float* __restrict__ dW = t.dW;
+  const long n = t.n;
+  const int msplit = t.msplit;
   long i4 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   long stride = (long)gridDim.x * blockDim.x * 4;
   for (; i4 + 4 <= n; i4 += stride) {
@@ -722,7 +821,19 @@ __global__ __launch_bounds__(256) void k_wgrad_batched(WgradBatchArgs a) {
   __shared__ WgradSmemT<TK3, TKO> smem;
   const bf16* X = (const bf16*)t.X;
   const bf16* Dz = (const bf16*)t.Dz;
-  if (t.vec)
+  // clipped tasks ride in the TK3 = 64 classes (bind.cpp, tk3_of); the task
+  // and so each of these tests is block-uniform
+  constexpr bool CL = TK3 == 64;
+  if (CL && ((t.p.R != t.p.Rf) | (t.p.S != t.p.Sf))) {
+    if (t.vec)
+      wgrad_tile<true, TK3, TKO, TR, CL>(X, Dz, t.out, t.p, t.mg, t.Ntot,
+                                         t.mchunk, tx, ty, z, t.msplit > 1,
+                                         smem);
+    else
+      wgrad_tile<false, TK3, TKO, TR, CL>(X, Dz, t.out, t.p, t.mg, t.Ntot,
+                                          t.mchunk, tx, ty, z, t.msplit > 1,
+                                          smem);
+  } else if (t.vec)
     wgrad_tile<true, TK3, TKO, TR>(X, Dz, t.out, t.p, t.mg, t.Ntot, t.mchunk,
                                    tx, ty, z, t.msplit > 1, smem);
   else
@@ -736,6 +847,11 @@ __global__ __launch_bounds__(256) void k_wgrad_reduce_batched(
   int i = 0;
   while (i + 1 < a.n && bid >= a.t[i + 1].base) i++;
   const WredTask& t = a.t[i];
+  if (t.Kd > 0) {  // block-uniform
+    const long begin = (long)(bid - t.base) * 1024;
+    wred_scatter(t, begin, min(t.n, begin + 1024), threadIdx.x, 256);
+    return;
+  }
   long i4 = ((long)(bid - t.base) * 256 + threadIdx.x) * 4;
   if (i4 + 4 <= t.n) {
     float4 v = *(const float4*)&t.ws[i4];
@@ -781,6 +897,15 @@ static inline int pick_splitk(int tiles, int Kd) {
 
 static inline int pick_tile(int M, int N);
 static inline int pick_tile_dgrad(int M, int N);
+// Tile class of one conv.  A clipped conv (tap window, a 1-2 pixel map)
+// takes the 64x64 latency tile: the CLIP kernels exist for that tile only.
+static inline int conv_tile(const ConvP& p) {
+  return taps_clipped(p) ? 0 : pick_tile(p.M, p.K);
+}
+// p: forward geometry
+static inline int conv_tile_dgrad(const ConvP& p) {
+  return taps_clipped(p) ? 0 : pick_tile_dgrad(p.Nb * p.H * p.W, p.C);
+}
 
 // Fill-split (HZ_SK_FILL / HZ_SK_FILL_DG, default 0 = off): when the
 // throughput 128x128 tile is picked but its grid lands under `fillmin`
@@ -807,9 +932,26 @@ static int fill_splitk(int blocks128, int Kd, int fillmin) {
 
 extern "C" int conv_fwd_splitk(ConvP p) {
   int tiles = cdiv_h(p.K, 64) * cdiv_h(p.M, 64);
+  // HZ_SK_CLIP_FULL=0: feed a clipped conv's window Kd to the picker below
+  // like any other conv (A/B knob; sweep in profiles/r10_fwd_split_policy.txt)
+  static const int clip_full = (int)env_long("HZ_SK_CLIP_FULL", 1);
+  if (clip_full && taps_clipped(p)) {
+    // A clipped conv keeps the dispatch class of its whole filter (split-K
+    // slabs + the owner BN at small M, which tests/test_bn_owner_gpu.py pins
+    // for the layer4 shapes): the decision is taken on the full Kd, and the
+    // window only shortens the K loop.  It never splits finer than the whole
+    // filter did — more slabs for less K would only add consumer traffic —
+    // nor finer than the window has K-steps.
+    const int kd_full = p.Rf * p.Sf * p.C;
+    int sk = pick_splitk(tiles, kd_full);
+    if (sk > 1) {
+      sk = cdiv_h(kd_full, cdiv_h(cdiv_h(kd_full, sk), 32) * 32);
+      sk = min(sk, cdiv_h(p.Kd, 32));
+    }
+    return sk;
+  }
   int sk = pick_splitk(tiles, p.Kd);
-  if (sk == 1 && sk_fill(0) > 0 && p.Kd >= 512
-      && pick_tile(p.M, p.K) == 2) {
+  if (sk == 1 && sk_fill(0) > 0 && p.Kd >= 512 && conv_tile(p) == 2) {
     int blocks = cdiv_h(p.M, 128) * cdiv_h(p.K, 128);
     if (blocks < sk_fill(0)) return fill_splitk(blocks, p.Kd, sk_fill(0));
   }
@@ -828,7 +970,7 @@ extern "C" int conv_dgrad_splitk(ConvP p) {
   int Kd = p.R * p.S * p.K;
   if (tiles >= tile_min_dg || Kd < kd_min_dg) {
     int M = p.Nb * p.H * p.W;
-    if (sk_fill(1) > 0 && Kd >= 512 && pick_tile_dgrad(M, p.C) == 2) {
+    if (sk_fill(1) > 0 && Kd >= 512 && conv_tile_dgrad(p) == 2) {
       int blocks = cdiv_h(M, 128) * cdiv_h(p.C, 128);
       if (blocks < sk_fill(1)) return fill_splitk(blocks, Kd, sk_fill(1));
     }
@@ -985,8 +1127,8 @@ static inline bool stem_eligible(const ConvP& p) {
   // savings.  Kept as an opt-in experiment + measured negative
   // (docs/STATUS.md); default OFF.
   static const int on = (int)env_long("HZ_STEM_DIRECT", 0);
-  return on && p.C == 3 && p.R == 7 && p.S == 7 && p.str == 2 &&
-         p.pad == 3 && p.K <= 64 && p.Wo <= 128;
+  return on && !taps_clipped(p) && p.C == 3 && p.R == 7 && p.S == 7 &&
+         p.str == 2 && p.pad == 3 && p.K <= 64 && p.Wo <= 128;
 }
 
 static void launch_stem_conv(const bf16* x, const bf16* w, bf16* y,
@@ -1060,22 +1202,23 @@ extern "C" void launch_conv_fwd(const void* x, const void* w, void* y,
   auto B = (const bf16*)w;
   auto Y = (bf16*)y;
   MagicP mg = make_magic(p, 1);
-  int tile = pick_tile(p.M, p.K);
-#define CASE_T(VA, VB, ST, TM, TN)                                     \
-  k_conv_mfma<1, VA, VB, ST, false, TM, TN><<<grid, 256, 0, st>>>(     \
-      A, B, Y, nullptr, stats, p, mg, p.K, 0, 0)
-#define DISPATCH(TM, TN)                                               \
-  do {                                                                 \
-    dim3 grid(cdiv_h(p.K, TN), cdiv_h(p.M, TM));                       \
-    if (vec && s) CASE_T(true, true, true, TM, TN);                    \
-    else if (vec) CASE_T(true, true, false, TM, TN);                   \
-    else if (s) CASE_T(false, false, true, TM, TN);                    \
-    else CASE_T(false, false, false, TM, TN);                          \
+  int tile = conv_tile(p);
+#define CASE_T(VA, VB, ST, TM, TN, CL)                                    \
+  k_conv_mfma<1, VA, VB, ST, false, TM, TN, false, CL>                    \
+      <<<grid, 256, 0, st>>>(A, B, Y, nullptr, stats, p, mg, p.K, 0, 0)
+#define DISPATCH(TM, TN, CL)                                              \
+  do {                                                                    \
+    dim3 grid(cdiv_h(p.K, TN), cdiv_h(p.M, TM));                          \
+    if (vec && s) CASE_T(true, true, true, TM, TN, CL);                   \
+    else if (vec) CASE_T(true, true, false, TM, TN, CL);                  \
+    else if (s) CASE_T(false, false, true, TM, TN, CL);                   \
+    else CASE_T(false, false, false, TM, TN, CL);                         \
   } while (0)
-  if (tile == 3) DISPATCH(256, 64);
-  else if (tile == 2) DISPATCH(128, 128);
-  else if (tile == 1) DISPATCH(128, 64);
-  else DISPATCH(64, 64);
+  if (tile == 3) DISPATCH(256, 64, false);
+  else if (tile == 2) DISPATCH(128, 128, false);
+  else if (tile == 1) DISPATCH(128, 64, false);
+  else if (taps_clipped(p)) DISPATCH(64, 64, true);
+  else DISPATCH(64, 64, false);
 #undef DISPATCH
 #undef CASE_T
 }
@@ -1092,20 +1235,29 @@ extern "C" void launch_conv_fwd_splitk(const void* x, const void* w,
   MagicP mg = make_magic(p, 1);
   // fill-split shapes keep their throughput tile; the classic small-M
   // split shapes pick tile 0 (64x64) as before
-  int tile = pick_tile(p.M, p.K);
-#define SK_T(VA, VB, TM, TN)                                              k_conv_mfma<1, VA, VB, false, true, TM, TN><<<grid, 256, 0, st>>>(          A, B, nullptr, ws, nullptr, p, mg, p.K, kchunk, 0)
-#define DISPATCH(TM, TN)                                                  do {                                                                      dim3 grid(cdiv_h(p.K, TN), cdiv_h(p.M, TM), splitk);                    if (vec) SK_T(true, true, TM, TN);                                      else SK_T(false, false, TM, TN);                                      } while (0)
-  if (tile == 3) DISPATCH(256, 64);
-  else if (tile == 2) DISPATCH(128, 128);
-  else if (tile == 1) DISPATCH(128, 64);
-  else DISPATCH(64, 64);
+  int tile = conv_tile(p);
+#define SK_T(VA, VB, TM, TN, CL)                                        \
+  k_conv_mfma<1, VA, VB, false, true, TM, TN, false, CL>                \
+      <<<grid, 256, 0, st>>>(A, B, nullptr, ws, nullptr, p, mg, p.K,    \
+                             kchunk, 0)
+#define DISPATCH(TM, TN, CL)                                            \
+  do {                                                                  \
+    dim3 grid(cdiv_h(p.K, TN), cdiv_h(p.M, TM), splitk);                \
+    if (vec) SK_T(true, true, TM, TN, CL);                              \
+    else SK_T(false, false, TM, TN, CL);                                \
+  } while (0)
+  if (tile == 3) DISPATCH(256, 64, false);
+  else if (tile == 2) DISPATCH(128, 128, false);
+  else if (tile == 1) DISPATCH(128, 64, false);
+  else if (taps_clipped(p)) DISPATCH(64, 64, true);
+  else DISPATCH(64, 64, false);
 #undef DISPATCH
 #undef SK_T
 }
 
 // KRSC-direct dgrad, one tile class: the split / non-split form and the
 // vector flags (A gathers vec8 along ko, B along c).
-template <int TM, int TN>
+template <int TM, int TN, bool CL = false>
 static void dgrad_krsc_t(const bf16* A, const bf16* B, bf16* dx, float* ws,
                          bool split, int splitk, int kchunk, const ConvP& p,
                          const MagicP& mg, int accum, hipStream_t st) {
@@ -1114,11 +1266,11 @@ static void dgrad_krsc_t(const bf16* A, const bf16* B, bf16* dx, float* ws,
 #define KRSC_T(VA, VB)                                                      \
   do {                                                                      \
     if (split)                                                              \
-      k_conv_mfma<2, VA, VB, false, true, TM, TN, true>                     \
+      k_conv_mfma<2, VA, VB, false, true, TM, TN, true, CL>                 \
           <<<grid, 256, 0, st>>>(A, B, nullptr, ws, nullptr, p, mg, p.C,    \
                                  kchunk, 0);                                \
     else                                                                    \
-      k_conv_mfma<2, VA, VB, false, false, TM, TN, true>                    \
+      k_conv_mfma<2, VA, VB, false, false, TM, TN, true, CL>                \
           <<<grid, 256, 0, st>>>(A, B, dx, nullptr, nullptr, p, mg, p.C, 0, \
                                  accum);                                    \
   } while (0)
@@ -1147,14 +1299,15 @@ extern "C" void launch_conv_dgrad(const void* dz, const void* w, void* dx,
       splitk = cdiv_h(p.Kd, kchunk);
     }
     MagicP mg = make_magic(p, 2);
-    int tile = pick_tile_dgrad(p.M, p.C);
-#define DISPATCH(TM, TN)                                                  \
-  dgrad_krsc_t<TM, TN>(A, B, (bf16*)dx, ws, split, splitk, kchunk, p, mg, \
-                       accum, st)
-    if (tile == 3) DISPATCH(256, 64);
-    else if (tile == 2) DISPATCH(128, 128);
-    else if (tile == 1) DISPATCH(128, 64);
-    else DISPATCH(64, 64);
+    int tile = conv_tile_dgrad(p);
+#define DISPATCH(TM, TN, CL)                                             \
+  dgrad_krsc_t<TM, TN, CL>(A, B, (bf16*)dx, ws, split, splitk, kchunk, p, \
+                           mg, accum, st)
+    if (tile == 3) DISPATCH(256, 64, false);
+    else if (tile == 2) DISPATCH(128, 128, false);
+    else if (tile == 1) DISPATCH(128, 64, false);
+    else if (taps_clipped(p)) DISPATCH(64, 64, true);
+    else DISPATCH(64, 64, false);
 #undef DISPATCH
     return;
   }
@@ -1162,31 +1315,42 @@ extern "C" void launch_conv_dgrad(const void* dz, const void* w, void* dx,
     int kchunk = cdiv_h(cdiv_h(p.Kd, splitk), 32) * 32;
     splitk = cdiv_h(p.Kd, kchunk);
     MagicP mg = make_magic(p, 2);
-    int tile = pick_tile_dgrad(p.M, p.C);
-#define SKD_T(VA, VB, TM, TN)                                             k_conv_mfma<2, VA, VB, false, true, TM, TN><<<grid, 256, 0, st>>>(          A, B, nullptr, ws, nullptr, p, mg, p.C, kchunk, 0)
-#define DISPATCH(TM, TN)                                                  do {                                                                      dim3 grid(cdiv_h(p.C, TN), cdiv_h(p.M, TM), splitk);                    if (vec) SKD_T(true, true, TM, TN);                                     else SKD_T(false, false, TM, TN);                                     } while (0)
-    if (tile == 3) DISPATCH(256, 64);
-    else if (tile == 2) DISPATCH(128, 128);
-    else if (tile == 1) DISPATCH(128, 64);
-    else DISPATCH(64, 64);
+    int tile = conv_tile_dgrad(p);
+#define SKD_T(VA, VB, TM, TN, CL)                                       \
+  k_conv_mfma<2, VA, VB, false, true, TM, TN, false, CL>                \
+      <<<grid, 256, 0, st>>>(A, B, nullptr, ws, nullptr, p, mg, p.C,    \
+                             kchunk, 0)
+#define DISPATCH(TM, TN, CL)                                            \
+  do {                                                                  \
+    dim3 grid(cdiv_h(p.C, TN), cdiv_h(p.M, TM), splitk);                \
+    if (vec) SKD_T(true, true, TM, TN, CL);                             \
+    else SKD_T(false, false, TM, TN, CL);                               \
+  } while (0)
+    if (tile == 3) DISPATCH(256, 64, false);
+    else if (tile == 2) DISPATCH(128, 128, false);
+    else if (tile == 1) DISPATCH(128, 64, false);
+    else if (taps_clipped(p)) DISPATCH(64, 64, true);
+    else DISPATCH(64, 64, false);
 #undef DISPATCH
 #undef SKD_T
   } else {
     MagicP mg = make_magic(p, 2);
-    int tile = pick_tile_dgrad(p.M, p.C);
-#define DGRAD_T(VA, VB, TM, TN)                                         \
-  k_conv_mfma<2, VA, VB, false, false, TM, TN><<<grid, 256, 0, st>>>(   \
-      A, B, (bf16*)dx, nullptr, nullptr, p, mg, p.C, 0, accum)
-#define DISPATCH(TM, TN)                                                \
+    int tile = conv_tile_dgrad(p);
+#define DGRAD_T(VA, VB, TM, TN, CL)                                     \
+  k_conv_mfma<2, VA, VB, false, false, TM, TN, false, CL>               \
+      <<<grid, 256, 0, st>>>(A, B, (bf16*)dx, nullptr, nullptr, p, mg,  \
+                             p.C, 0, accum)
+#define DISPATCH(TM, TN, CL)                                            \
   do {                                                                  \
     dim3 grid(cdiv_h(p.C, TN), cdiv_h(p.M, TM));                        \
-    if (vec) DGRAD_T(true, true, TM, TN);                               \
-    else DGRAD_T(false, false, TM, TN);                                 \
+    if (vec) DGRAD_T(true, true, TM, TN, CL);                           \
+    else DGRAD_T(false, false, TM, TN, CL);                             \
   } while (0)
-    if (tile == 3) DISPATCH(256, 64);
-    else if (tile == 2) DISPATCH(128, 128);
-    else if (tile == 1) DISPATCH(128, 64);
-    else DISPATCH(64, 64);
+    if (tile == 3) DISPATCH(256, 64, false);
+    else if (tile == 2) DISPATCH(128, 128, false);
+    else if (tile == 1) DISPATCH(128, 64, false);
+    else if (taps_clipped(p)) DISPATCH(64, 64, true);
+    else DISPATCH(64, 64, false);
 #undef DISPATCH
 #undef DGRAD_T
   }
@@ -1258,21 +1422,29 @@ extern "C" void launch_wgrad(const void* x, const void* dz, float* dw,
   bool vec = (p.C % 8) == 0;
   float* out = msplit > 1 ? ws : dw;
   MagicP mg = make_magic(p, 1);
-#define WGRAD_T(VA, TR)                                               \
-  k_wgrad<VA, TR><<<grid, 256, 0, st>>>((const bf16*)x, (const bf16*)dz, \
-                                        out, p, mg, p.K, mchunk)
-#define DISPATCH(TR)            \
-  do {                          \
-    if (vec) WGRAD_T(true, TR); \
-    else WGRAD_T(false, TR);    \
+#define WGRAD_T(VA, TR, CL)                                           \
+  k_wgrad<VA, TR, CL><<<grid, 256, 0, st>>>(                          \
+      (const bf16*)x, (const bf16*)dz, out, p, mg, p.K, mchunk)
+#define DISPATCH(TR, CL)            \
+  do {                              \
+    if (vec) WGRAD_T(true, TR, CL); \
+    else WGRAD_T(false, TR, CL);    \
   } while (0)
-  if (tr) DISPATCH(true);
-  else DISPATCH(false);
+  if (taps_clipped(p)) {
+    if (tr) DISPATCH(true, true);
+    else DISPATCH(false, true);
+  } else if (tr) DISPATCH(true, false);
+  else DISPATCH(false, false);
 #undef DISPATCH
 #undef WGRAD_T
   if (msplit > 1) {
-    long n = (long)p.K * p.Kd;
-    int blocks = (int)min((n / 4 + 255) / 256, (long)1024);
-    k_wgrad_reduce<<<blocks, 256, 0, st>>>(ws, dw, n, msplit);
+    WredTask t{};
+    t.ws = ws;
+    t.dW = dw;
+    t.n = (long)p.K * p.Kd;
+    t.msplit = msplit;
+    wred_set_window(&t, p);
+    int blocks = (int)max(1L, min((t.n / 4 + 255) / 256, (long)1024));
+    k_wgrad_reduce<<<blocks, 256, 0, st>>>(t);
   }
 }

@@ -19,6 +19,10 @@ struct ConvP {
   int Ho, Wo, R, S;        // output spatial, filter
   int str, pad;
   int M, Kd;               // GEMM rows, reduction size
+  // Tap window (clip_taps below).  R, S, Kd describe the window the kernels
+  // loop over; the filter in memory is Rf×Sf and the window starts at tap
+  // (r0, s0).  Unclipped: r0 = s0 = 0, Rf = R, Sf = S.
+  int r0, s0, Rf, Sf;
 };
 
 // Fast division by a runtime constant (cutlass FastDivmod form):
@@ -57,7 +61,23 @@ struct WredTask {
   long n;
   int msplit;
   int base;  // first block id; each block covers 1024 floats
+  // Clipped task (Kd > 0): the slabs are dense [K][Kd] over the tap window
+  // and dW is the full filter.  Slab element (ko, k3) lands at
+  //   ko*KdF + org + k3 + (k3 / SC)*skip
+  // with SC = S*C, KdF = Rf*Sf*C, org = (r0*Sf + s0)*C, skip = (Sf - S)*C.
+  // Kd == 0: dW index = slab index.
+  int Kd, SC, KdF, org, skip;
 };
+
+// Fills the scatter fields of a slab-reduce task from the conv's geometry.
+inline void wred_set_window(WredTask* t, const ConvP& p) {
+  const bool clipped = p.R != p.Rf || p.S != p.Sf;
+  t->Kd = clipped ? p.Kd : 0;
+  t->SC = p.S * p.C;
+  t->KdF = p.Rf * p.Sf * p.C;
+  t->org = (p.r0 * p.Sf + p.s0) * p.C;
+  t->skip = (p.Sf - p.S) * p.C;
+}
 
 struct WredBatchArgs {
   int n;
@@ -106,6 +126,50 @@ inline MagicP make_magic(const ConvP& p, int mode) {
     magic_u32(mg.d[i], &mg.m[i], &mg.s[i]);
   }
   return mg;
+}
+
+// -------------------------------------------------------------- tap window --
+// Filter taps that only ever meet padding: tap row r is live iff some output
+// row ho in [0, Ho) reads a real input row, 0 <= ho*str - pad + r < H.
+// Returns the bounding range [*lo, *lo + *n) of the live taps of one axis
+// (a dead tap inside the range stays and multiplies zeros); n == 0 when no
+// tap is live.
+inline void tap_range(int H, int Ho, int R, int str, int pad, int* lo,
+                      int* n) {
+  int first = R, last = -1;
+  for (int r = 0; r < R; r++)
+    for (int ho = 0; ho < Ho; ho++) {
+      const int hi = ho * str - pad + r;
+      if (hi >= 0 && hi < H) {
+        if (r < first) first = r;
+        last = r;
+        break;
+      }
+    }
+  *lo = last < 0 ? 0 : first;
+  *n = last < 0 ? 0 : last - first + 1;
+}
+
+// Clips a full-filter ConvP (Rf = R, Sf = S, r0 = s0 = 0) to its tap window:
+// R, S, Kd become the window's and (r0, s0) its origin in the Rf×Sf filter.
+// The (input pixel, output pixel, tap) relation is the same in forward,
+// dgrad and wgrad, so one window serves all three.  Ho, Wo, M keep the full
+// filter's values.  A conv with no live tap on an axis is left unclipped.
+inline ConvP clip_taps(ConvP p) {
+  int r0, rn, s0, sn;
+  tap_range(p.H, p.Ho, p.Rf, p.str, p.pad, &r0, &rn);
+  tap_range(p.W, p.Wo, p.Sf, p.str, p.pad, &s0, &sn);
+  if (rn <= 0 || sn <= 0) return p;
+  p.r0 = r0;
+  p.s0 = s0;
+  p.R = rn;
+  p.S = sn;
+  p.Kd = rn * sn * p.C;
+  return p;
+}
+
+inline bool taps_clipped(const ConvP& p) {
+  return p.R != p.Rf || p.S != p.Sf;
 }
 
 // ------------------------------------------------------- environment knobs --
