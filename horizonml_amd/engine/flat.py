@@ -19,6 +19,12 @@ buffers, single-kernel updates):
   through a segment table: one segment per parameter, cut into chunks of at
   most ``SEG_CHUNK`` elements, one workgroup per chunk (docs/KERNELS.md,
   "Segmented step").  Built only when an optimizer asks for it.
+* Filter taps that only ever meet padding (ResNet18 at 32x32: 62 % of the
+  buffer) have a zero gradient for good; without weight decay the step is the
+  identity on them.  The manager keeps a chunk table of the live ranges,
+  built from the native tap-window registry and verified against the device
+  state, and the unsegmented decay-free step streams only those
+  (docs/KERNELS.md, "Live-range step").
 """
 from __future__ import annotations
 
@@ -105,6 +111,96 @@ class _SegState:
         return float(self.norm_out[0].cpu())
 
 
+LIVE_CHUNK = 4096  # elements per chunk = per workgroup of the *_live kernels
+
+
+def build_live_chunks(numel, windows, chunk: int = LIVE_CHUNK):
+    """Chunk table of the live part of a flat buffer of ``numel`` elements.
+
+    ``windows``: ``(offset, K, Rf, Sf, C, r0, R, s0, S)`` per conv weight —
+    a KRSC filter ``[K, Rf, Sf, C]`` at ``offset`` whose taps outside rows
+    ``[r0, r0+R)`` × columns ``[s0, s0+S)`` are dead.  Everything else of the
+    buffer is live, and live spans run across parameter boundaries.
+
+    Returns ``(chunks, n_dead)``: ``chunks`` a list of ``(start, run_len,
+    run_pitch, nruns)`` — elements ``start + r*run_pitch + j`` for
+    ``r < nruns``, ``j < run_len``, at most ``chunk`` of them — that covers
+    every live element exactly once and no dead one.  A clipped filter's live
+    elements are, per window row, K runs of ``S*C`` at pitch ``Rf*Sf*C`` (one
+    run of ``R*Sf*C`` per filter when the window spans the filter's width);
+    a chunk groups as many whole runs as fit, and a run longer than a chunk
+    is cut.  Every chunk is checked against ``numel`` here, on the host: the
+    kernels index the flat buffers with the table unchecked."""
+    numel, chunk = int(numel), int(chunk)
+    if numel < 1 or numel >= 2 ** 31 or chunk < 1:
+        raise ValueError("live table offsets are int32")
+    spans, families, cursor, n_dead = [], [], 0, 0
+    for off, K, Rf, Sf, C, r0, R, s0, S in sorted(
+            tuple(int(x) for x in w) for w in windows):
+        kdf = Rf * Sf * C
+        if min(K, Rf, Sf, C, R, S) < 1 or min(r0, s0) < 0 \
+                or r0 + R > Rf or s0 + S > Sf:
+            raise ValueError("tap window outside its filter")
+        if off < cursor or off + K * kdf > numel:
+            raise ValueError("conv weights overlap or leave the buffer")
+        if R == Rf and S == Sf:
+            continue  # fully live: stays inside the surrounding span
+        if off > cursor:
+            spans.append((cursor, off))
+        cursor = off + K * kdf
+        n_dead += K * (Rf * Sf - R * S) * C
+        if S == Sf:
+            families.append((off + r0 * Sf * C, R * Sf * C, kdf, K))
+        else:
+            families += [(off + ((r0 + r) * Sf + s0) * C, S * C, kdf, K)
+                         for r in range(R)]
+    if cursor < numel:
+        spans.append((cursor, numel))
+
+    chunks = []
+
+    def cut(lo, hi):
+        chunks.extend((o, min(chunk, hi - o), 0, 1)
+                      for o in range(lo, hi, chunk))
+
+    for lo, hi in spans:
+        cut(lo, hi)
+    for start, run_len, pitch, nruns in families:
+        if run_len >= chunk or nruns == 1:
+            for r in range(nruns):
+                cut(start + r * pitch, start + r * pitch + run_len)
+            continue
+        group = chunk // run_len
+        chunks.extend((start + r * pitch, run_len, pitch,
+                       min(group, nruns - r))
+                      for r in range(0, nruns, group))
+    for start, run_len, pitch, nruns in chunks:
+        if not (run_len >= 1 and nruns >= 1 and run_len * nruns <= chunk
+                and start >= 0 and pitch >= 0
+                and (nruns == 1 or pitch >= run_len)
+                and start + (nruns - 1) * pitch + run_len <= numel):
+            raise AssertionError("live chunk out of bounds")
+    return chunks, n_dead
+
+
+class _LiveTable:
+    """The manager's live table and what it was built from: the registry
+    version, and the per-element buffers (optimizer state, probe ``prev``,
+    bf16 gradient) whose dead elements were verified zero at that build."""
+
+    def __init__(self):
+        self.version = -1          # -1: not built, or invalidated
+        self.bufs = []             # verified at the last build
+        self.chunks = None         # int32 [nchunks, 4] on the device, or None
+        self.n_dead = 0
+        self.n_demoted = 0         # clipped convs that failed the check
+        self.nchunks = 0
+
+    def covers(self, bufs):
+        have = {t.data_ptr() for t in self.bufs}
+        return all(t.data_ptr() in have for t in bufs)
+
+
 def _seg_state(mgr, wd, no_decay_1d, max_norm, lars=False, eta=1e-3):
     if max_norm < 0 or eta <= 0:
         raise ValueError("clip_grad_norm must be >= 0 and lars_eta > 0")
@@ -125,6 +221,9 @@ class FlatParamManager:
         self.numel = total
         self.master = torch.zeros(total, device=device)
         self.grad = torch.zeros(total, device=device)
+        # tap windows recorded at these addresses belong to a freed model
+        _ops.extension().tap_window_reset(
+            self.grad.data_ptr(), self.grad.data_ptr() + 4 * total)
         self.shadow = torch.zeros(total, device=device, dtype=torch.bfloat16)
         self.slices = {}
         off = 0
@@ -152,6 +251,11 @@ class FlatParamManager:
         # BN-stats arena: one pre-zeroed f32 slab per conv ([2K] each),
         # re-zeroed by the fused optimizer kernel each step (no per-conv
         # fill kernels in the forward).
+        # conv weights by offset: what a tap-window registry entry must match
+        # to count for this manager (live table, below)
+        self._conv_shapes = {woff: tuple(m.weight.shape)
+                             for m, woff, _ in convs}
+        self._live = _LiveTable()
         stats_total = sum(2 * m.out_ch for m, _, _ in convs)
         self.stats_arena = torch.zeros(max(1, stats_total), device=device)
         soff = 0
@@ -210,6 +314,97 @@ class FlatParamManager:
                 self.master.device)
         return self._seg_tables[key]
 
+    # -- live table: the fused step skips dead filter taps -------------------
+    def live_windows(self):
+        """``(offset, K, Rf, Sf, C, r0, R, s0, S)`` of every conv weight of
+        this manager the native tap-window registry knows, by offset.  An
+        entry counts only when its pointer is a conv weight's gradient view
+        of this manager and the filter shape agrees; a conv without one is
+        fully live."""
+        base, out = self.grad.data_ptr(), []
+        for ptr, K, Rf, Sf, C, r0, R, s0, S in \
+                _ops.extension().tap_window_registry():
+            off, rem = divmod(ptr - base, 4)
+            if rem == 0 and self._conv_shapes.get(off) == (K, Rf, Sf, C):
+                out.append((off, K, Rf, Sf, C, r0, R, s0, S))
+        return sorted(out)
+
+    def invalidate_live_table(self):
+        """The next eager ``step`` rebuilds (and re-verifies) the table; a
+        captured one launches the full-range kernel until then."""
+        self._live.version = -1
+
+    def live_table_info(self):
+        """State of the live table: ``state`` is ``"unbuilt"``, ``"none"``
+        (built, no dead element: the full-range kernels run) or ``"live"``;
+        ``skipped`` elements per step, ``nchunks``, and ``demoted``, the
+        clipped convs kept fully live because their dead state was not
+        zero."""
+        lt = self._live
+        state = ("unbuilt" if lt.version < 0
+                 else "none" if lt.chunks is None else "live")
+        return {"state": state, "version": lt.version,
+                "skipped": lt.n_dead if state == "live" else 0,
+                "nchunks": lt.nchunks if state == "live" else 0,
+                "demoted": lt.n_demoted}
+
+    def live_chunks(self, bufs):
+        """The live table for a step that streams ``bufs`` (optimizer state,
+        probe ``prev``, bf16 gradient; ``None`` entries ignored) besides
+        master, grad and shadow — or ``None`` when the step must launch the
+        full-range kernel: switched off, nothing dead, or stale while the
+        stream is capturing.  Stale outside capture: rebuilt here."""
+        ext = _ops.extension()
+        if not ext.opt_skip_dead_enabled():
+            return None
+        lt = self._live
+        bufs = [t for t in bufs if t is not None]
+        version = ext.tap_window_version()
+        if lt.version != version or not lt.covers(bufs):
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            have = {t.data_ptr() for t in bufs}
+            bufs += [t for t in lt.bufs if t.data_ptr() not in have]
+            self._build_live_table(version, bufs)
+        return lt.chunks
+
+    def _build_live_table(self, version, bufs):
+        """Not in the hot loop: one reduction with one host sync verifies
+        the identity precondition on the device state itself — grad and
+        every buffer of ``bufs`` hold the bit pattern of +0 on every dead
+        element (so g = m = v = 0 there and, without weight decay, the
+        update is the identity).  A conv that fails is kept fully live.
+        Then shadow = bf16(master) over the whole buffer, once: the skipped
+        elements hold what the full kernel would have written."""
+        lt = self._live
+        wins = self.live_windows()
+        clipped = [w for w in wins if w[6] * w[8] < w[2] * w[3]]
+        lt.n_demoted = 0
+        if clipped:
+            counts = []
+            for off, K, Rf, Sf, C, r0, R, s0, S in clipped:
+                n, c = K * Rf * Sf * C, 0
+                for t in [self.grad] + bufs:
+                    bits = t[off:off + n].view(
+                        torch.int32 if t.element_size() == 4 else torch.int16
+                    ).view(K, Rf, Sf, C)
+                    c = c + torch.count_nonzero(bits) - torch.count_nonzero(
+                        bits[:, r0:r0 + R, s0:s0 + S])
+                counts.append(c)
+            bad = torch.stack(counts).cpu().tolist()
+            lt.n_demoted = sum(1 for b in bad if b)
+            clipped = [w for w, b in zip(clipped, bad) if not b]
+        chunks, lt.n_dead = build_live_chunks(self.numel, clipped)
+        if lt.n_dead:
+            lt.chunks = torch.tensor(chunks, dtype=torch.int32,
+                                     device=self.master.device)
+            lt.nchunks = len(chunks)
+            with torch.no_grad():
+                self.shadow.copy_(self.master)
+        else:
+            lt.chunks, lt.nchunks = None, 0
+        lt.version, lt.bufs = version, bufs
+
 
 def _sched_buffers(schedule, dev):
     """Device residents of a scheduled optimizer: the f32 lr table the kernel
@@ -252,6 +447,7 @@ class HorizonAdam:
         self.v = torch.zeros_like(mgr.master)
         self.step_t = torch.zeros(1, device=dev)
         self.lr_table, self.lr_out = _sched_buffers(schedule, dev)
+        self._live_stale = False  # set by load_state_dict
 
     def step(self, zero_grad: bool = True, grad_bf16=None,
              grad_scale: float = 1.0, probe=None):
@@ -263,6 +459,9 @@ class HorizonAdam:
         ext = _ops.extension()
         ext.flush_wgrad()  # batched deferred weight grads
         p0, p1, p2 = probe if probe is not None else (None, None, None)
+        if self._live_stale:
+            self.mgr.invalidate_live_table()
+            self._live_stale = False
         if self.seg is not None:
             self.seg.reduce(ext, self.mgr, grad_bf16, grad_scale)
             ext.adam_step_seg(self.mgr.master, self.mgr.grad, self.m, self.v,
@@ -272,6 +471,16 @@ class HorizonAdam:
                               zero_grad, self.seg.table.chunks,
                               self.seg.seg_mul, self.mgr.stats_arena,
                               grad_bf16, grad_scale, p0, p1, p2)
+        elif self.wd == 0 and (live := self.mgr.live_chunks(
+                (self.m, self.v, p0, grad_bf16))) is not None:
+            # no decay of either kind: dead filter taps keep their value,
+            # only the live ranges are streamed (k_adam_step_live)
+            ext.adam_step_live(self.mgr.master, self.mgr.grad, self.m,
+                               self.v, self.mgr.shadow, self.step_t,
+                               self.lr_table, self.lr_out, self.lr,
+                               self.betas[0], self.betas[1], self.eps,
+                               zero_grad, live, self.mgr.stats_arena,
+                               grad_bf16, grad_scale, p0, p1, p2)
         elif self.schedule is None and not self.decoupled:
             ext.adam_step(self.mgr.master, self.mgr.grad, self.m,
                           self.v, self.mgr.shadow, self.step_t,
@@ -319,6 +528,7 @@ class HorizonAdam:
     def load_state_dict(self, state):
         if state.get("kind") != "horizon_adam":
             raise ValueError("checkpoint optimizer state is not HorizonAdam")
+        self._live_stale = True  # loaded moments: verify the table again
         with torch.no_grad():
             self.m.copy_(state["m"].to(self.m.device))
             self.v.copy_(state["v"].to(self.v.device))
@@ -355,6 +565,7 @@ class HorizonSGD:
         self.lr_table, self.lr_out = _sched_buffers(schedule, dev)
         self.step_t = (torch.zeros(1, device=dev)
                        if schedule is not None else None)
+        self._live_stale = False  # set by load_state_dict
 
     def step(self, zero_grad: bool = True, grad_bf16=None,
              grad_scale: float = 1.0, probe=None):
@@ -363,6 +574,9 @@ class HorizonSGD:
         ext = _ops.extension()
         ext.flush_wgrad()  # batched deferred weight grads
         p0, p1, p2 = probe if probe is not None else (None, None, None)
+        if self._live_stale:
+            self.mgr.invalidate_live_table()
+            self._live_stale = False
         if self.seg is not None:
             self.seg.reduce(ext, self.mgr, grad_bf16, grad_scale)
             ext.sgd_step_seg(self.mgr.master, self.mgr.grad, self.mom,
@@ -371,6 +585,13 @@ class HorizonSGD:
                              zero_grad, self.seg.table.chunks,
                              self.seg.seg_mul, grad_bf16, grad_scale,
                              p0, p1, p2)
+        elif self.wd == 0 and (live := self.mgr.live_chunks(
+                (self.mom, p0, grad_bf16))) is not None:
+            ext.sgd_step_live(self.mgr.master, self.mgr.grad, self.mom,
+                              self.mgr.shadow, self.step_t, self.lr_table,
+                              self.lr_out, self.lr, self.mu, self.nesterov,
+                              zero_grad, live, grad_bf16, grad_scale,
+                              p0, p1, p2)
         elif self.schedule is None and not self.nesterov:
             ext.sgd_step(self.mgr.master, self.mgr.grad, self.mom,
                          self.mgr.shadow, self.lr, self.mu, self.wd,
@@ -420,6 +641,7 @@ class HorizonSGD:
             raise ValueError("checkpoint optimizer state is not HorizonSGD")
         if (state.get("mom") is None) != (self.mom is None):
             raise ValueError("momentum buffer mismatch with checkpoint")
+        self._live_stale = True  # loaded momentum: verify the table again
         with torch.no_grad():
             if self.mom is not None:
                 self.mom.copy_(state["mom"].to(self.mom.device))

@@ -5,7 +5,10 @@
 #include <c10/hip/HIPStream.h>
 #include <c10/hip/HIPCachingAllocator.h>
 
+#include <algorithm>
 #include <memory>
+#include <mutex>
+#include <unordered_map>
 #include <vector>
 
 #include "launch.h"  // ABI structs, launcher declarations, env_long
@@ -86,6 +89,90 @@ std::vector<int64_t> conv_tap_window(int64_t H, int64_t W, int64_t R,
   p = clip_taps(p);
   return {p.r0, p.s0, p.R, p.S};
 }
+
+// ---- tap-window registry ----------------------------------------------------
+// What the fused optimizer needs to skip dead filter taps (engine/flat.py,
+// live table): per weight-gradient buffer, the filter shape and the union of
+// the tap windows of every geometry its conv has run a direct-grad backward
+// at.  Host bookkeeping only: nothing is launched or allocated on the device,
+// so it runs the same under graph capture.  Monotone: a window only widens;
+// the version counts creations and growths.
+struct TapWindow {
+  int K, Rf, Sf, C;
+  int r0, R, s0, S;
+};
+std::mutex g_tapwin_mu;  // backward runs on autograd's device thread
+std::unordered_map<uintptr_t, TapWindow> g_tapwin;
+int64_t g_tapwin_version = 0;
+
+void record_tap_window(const Tensor& dw, const ConvP& p) {
+  const ConvP g = geometric_taps(p);
+  const uintptr_t key = (uintptr_t)dw.data_ptr();
+  std::lock_guard<std::mutex> lock(g_tapwin_mu);
+  auto it = g_tapwin.find(key);
+  if (it == g_tapwin.end() || it->second.K != g.K || it->second.Rf != g.Rf ||
+      it->second.Sf != g.Sf || it->second.C != g.C) {
+    // new buffer, or its address now belongs to another filter
+    g_tapwin[key] = {g.K, g.Rf, g.Sf, g.C, g.r0, g.R, g.s0, g.S};
+    g_tapwin_version++;
+    return;
+  }
+  TapWindow& w = it->second;
+  const int r0 = std::min(w.r0, g.r0), s0 = std::min(w.s0, g.s0);
+  const int r1 = std::max(w.r0 + w.R, g.r0 + g.R);
+  const int s1 = std::max(w.s0 + w.S, g.s0 + g.S);
+  if (r0 != w.r0 || s0 != w.s0 || r1 - r0 != w.R || s1 - s0 != w.S) {
+    w.r0 = r0;
+    w.R = r1 - r0;
+    w.s0 = s0;
+    w.S = s1 - s0;
+    g_tapwin_version++;
+  }
+}
+
+// [(grad data pointer, K, Rf, Sf, C, r0, R, s0, S)], in no particular order
+std::vector<std::vector<int64_t>> tap_window_registry() {
+  std::lock_guard<std::mutex> lock(g_tapwin_mu);
+  std::vector<std::vector<int64_t>> out;
+  out.reserve(g_tapwin.size());
+  for (const auto& kv : g_tapwin) {
+    const TapWindow& w = kv.second;
+    out.push_back({(int64_t)kv.first, w.K, w.Rf, w.Sf, w.C, w.r0, w.R, w.s0,
+                   w.S});
+  }
+  return out;
+}
+
+int64_t tap_window_version() {
+  std::lock_guard<std::mutex> lock(g_tapwin_mu);
+  return g_tapwin_version;
+}
+
+// Forget the windows of the buffers at addresses [lo, hi); every window when
+// hi <= lo.  A manager calls it over its freshly allocated gradient buffer,
+// whose addresses may have served another model's filters before.  The
+// version still moves forward, so a table built from the old entries reads
+// as stale.
+void tap_window_reset(int64_t lo, int64_t hi) {
+  std::lock_guard<std::mutex> lock(g_tapwin_mu);
+  if (hi <= lo) {
+    g_tapwin.clear();
+  } else {
+    for (auto it = g_tapwin.begin(); it != g_tapwin.end();)
+      if (it->first >= (uintptr_t)lo && it->first < (uintptr_t)hi)
+        it = g_tapwin.erase(it);
+      else
+        ++it;
+  }
+  g_tapwin_version++;
+}
+
+// Live-range optimizer step (engine/flat.py): HZ_OPT_SKIP_DEAD (read at
+// load, default on); off = the optimizers launch the full-range kernels,
+// kept for A/B timing and as the tests' reference.
+bool g_opt_skip_dead = env_long("HZ_OPT_SKIP_DEAD", 1) != 0;
+void set_opt_skip_dead(bool on) { g_opt_skip_dead = on; }
+bool opt_skip_dead_enabled() { return g_opt_skip_dead; }
 
 // ---- deferred (batched) wgrad ---------------------------------------------
 // The weight-gradient GEMMs are off the backward's critical chain (nothing
@@ -605,6 +692,7 @@ std::vector<Tensor> conv_bn_act_bwd(
 
   Tensor dw = direct ? *dw_out
                      : at::zeros({(int64_t)K, R, S, (int64_t)p.C}, fopt);
+  if (direct) record_tap_window(dw, p);
   if (direct && g_wgrad_defer) {
     g_pending.push_back({x, dconv, dw, p});  // runs batched at flush_wgrad
   } else {
@@ -1213,6 +1301,91 @@ void sgd_step_seg(Tensor master, Tensor grad, c10::optional<Tensor> mom,
                       t.nchunks, t.seg_mul, cur_stream());
 }
 
+// Live-range forms: the unsegmented step with weight decay 0 over the chunks
+// of `live` only.  live int32 [nchunks,4] = (start, run_len, run_pitch,
+// nruns) comes from engine/flat.build_live_chunks, which checks every chunk
+// against the buffer size on the host before the table is uploaded; the
+// device table is not re-read here.
+const int* live_table(const Tensor& live, const Tensor& master,
+                      int* nchunks) {
+  TORCH_CHECK(live.scalar_type() == torch::kInt32 && live.dim() == 2
+                  && live.size(1) == 4 && live.size(0) >= 1
+                  && live.is_contiguous()
+                  && live.device() == master.device()
+                  && (uintptr_t)live.data_ptr() % 16 == 0,
+              "live must be a contiguous, 16-byte aligned int32 [nchunks,4] "
+              "tensor on master's device");
+  *nchunks = (int)live.size(0);
+  return live.data_ptr<int>();
+}
+
+void adam_step_live(Tensor master, Tensor grad, Tensor m, Tensor v,
+                    c10::optional<Tensor> shadow, Tensor step_t,
+                    c10::optional<Tensor> lr_table,
+                    c10::optional<Tensor> lr_out, double lr, double b1,
+                    double b2, double eps, bool zero_grad, Tensor live,
+                    c10::optional<Tensor> extra_zero,
+                    c10::optional<Tensor> grad_bf16, double grad_scale,
+                    c10::optional<Tensor> probe_prev,
+                    c10::optional<Tensor> probe_sumsq,
+                    c10::optional<Tensor> probe_out) {
+  check_f32(master, "master");
+  check_probe(probe_prev, probe_sumsq, probe_out);
+  TORCH_CHECK(grad.numel() == master.numel() && m.numel() == master.numel()
+                  && v.numel() == master.numel(),
+              "grad / m / v must match master's size");
+  int nchunks = 0;
+  const int* chunks = live_table(live, master, &nchunks);
+  long T = 0;
+  const float* table = sched_table(lr_table, master, &T);
+  float* out = sched_scalar(lr_out, master, "lr_out");
+  float* st = sched_scalar(step_t, master, "step_t");
+  launch_adam_step_live(master.data_ptr<float>(), grad.data_ptr<float>(),
+                        m.data_ptr<float>(), v.data_ptr<float>(),
+                        opt_ptr(shadow), st, (float)lr, (float)b1, (float)b2,
+                        (float)eps, zero_grad ? 1 : 0,
+                        opt_ptr<float>(extra_zero),
+                        extra_zero.has_value() ? extra_zero->numel() : 0,
+                        opt_ptr(grad_bf16), (float)grad_scale,
+                        opt_ptr<float>(probe_prev),
+                        opt_ptr<float>(probe_sumsq),
+                        opt_ptr<float>(probe_out), table, T, out, chunks,
+                        nchunks, cur_stream());
+}
+
+void sgd_step_live(Tensor master, Tensor grad, c10::optional<Tensor> mom,
+                   c10::optional<Tensor> shadow, c10::optional<Tensor> step_t,
+                   c10::optional<Tensor> lr_table,
+                   c10::optional<Tensor> lr_out, double lr, double mu,
+                   bool nesterov, bool zero_grad, Tensor live,
+                   c10::optional<Tensor> grad_bf16, double grad_scale,
+                   c10::optional<Tensor> probe_prev,
+                   c10::optional<Tensor> probe_sumsq,
+                   c10::optional<Tensor> probe_out) {
+  check_f32(master, "master");
+  check_probe(probe_prev, probe_sumsq, probe_out);
+  TORCH_CHECK(grad.numel() == master.numel()
+                  && (!mom.has_value() || mom->numel() == master.numel()),
+              "grad / mom must match master's size");
+  TORCH_CHECK(!nesterov || (mom.has_value() && mu > 0.0),
+              "nesterov needs a momentum buffer and momentum > 0");
+  int nchunks = 0;
+  const int* chunks = live_table(live, master, &nchunks);
+  long T = 0;
+  const float* table = sched_table(lr_table, master, &T);
+  TORCH_CHECK(table == nullptr || step_t.has_value(),
+              "lr_table needs the step_t device counter");
+  float* out = sched_scalar(lr_out, master, "lr_out");
+  float* st = sched_scalar(step_t, master, "step_t");
+  launch_sgd_step_live(master.data_ptr<float>(), grad.data_ptr<float>(),
+                       opt_ptr<float>(mom), opt_ptr(shadow), (float)lr,
+                       (float)mu, zero_grad ? 1 : 0, opt_ptr(grad_bf16),
+                       (float)grad_scale, opt_ptr<float>(probe_prev),
+                       opt_ptr<float>(probe_sumsq), opt_ptr<float>(probe_out),
+                       st, table, T, out, nesterov ? 1 : 0, chunks, nchunks,
+                       cur_stream());
+}
+
 void permute_krsc_rsck(Tensor src, Tensor dst, Tensor meta,
                        int64_t max_elem) {
   TORCH_CHECK(meta.scalar_type() == torch::kInt32 && meta.is_cuda());
@@ -1424,6 +1597,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("grad_scale") = 1.0, py::arg("probe_prev") = py::none(),
         py::arg("probe_sumsq") = py::none(),
         py::arg("probe_out") = py::none());
+  m.def("adam_step_live", &adam_step_live, py::arg("master"),
+        py::arg("grad"), py::arg("m"), py::arg("v"), py::arg("shadow"),
+        py::arg("step_t"), py::arg("lr_table"), py::arg("lr_out"),
+        py::arg("lr"), py::arg("b1"), py::arg("b2"), py::arg("eps"),
+        py::arg("zero_grad"), py::arg("live"),
+        py::arg("extra_zero") = py::none(), py::arg("grad_bf16") = py::none(),
+        py::arg("grad_scale") = 1.0, py::arg("probe_prev") = py::none(),
+        py::arg("probe_sumsq") = py::none(),
+        py::arg("probe_out") = py::none());
+  m.def("sgd_step_live", &sgd_step_live, py::arg("master"), py::arg("grad"),
+        py::arg("mom"), py::arg("shadow"), py::arg("step_t"),
+        py::arg("lr_table"), py::arg("lr_out"), py::arg("lr"), py::arg("mu"),
+        py::arg("nesterov"), py::arg("zero_grad"), py::arg("live"),
+        py::arg("grad_bf16") = py::none(), py::arg("grad_scale") = 1.0,
+        py::arg("probe_prev") = py::none(),
+        py::arg("probe_sumsq") = py::none(),
+        py::arg("probe_out") = py::none());
+  m.def("tap_window_registry", &tap_window_registry);
+  m.def("tap_window_version", &tap_window_version);
+  m.def("tap_window_reset", &tap_window_reset, py::arg("lo") = 0,
+        py::arg("hi") = 0);
+  m.def("set_opt_skip_dead", &set_opt_skip_dead);
+  m.def("opt_skip_dead_enabled", &opt_skip_dead_enabled);
   m.def("permute_krsc_rsck", &permute_krsc_rsck);
   m.def("grad_divergence", &grad_divergence);
   m.def("normalize_u8", &normalize_u8);

@@ -1748,7 +1748,34 @@ __global__ __launch_bounds__(256) void k_ce_ls_fwd_bwd(
 // ratio).  The scale is its own rounded product in front of the unchanged
 // expression, skipped when gmul == 1, so a uniform table reproduces the
 // unsegmented kernels bit for bit.
-template <bool DECOUPLED, bool SEG = false>
+// LIVE (the *_live kernels): the range is a chunk of the live table, `nruns`
+// runs of `run_len` elements at pitch `run_pitch` from `base`; [i0, n) then
+// counts the chunk's elements (n = nruns·run_len) and LiveIdx turns the count
+// into the buffer index.  Everything else is the same loop.
+struct LiveIdx {
+  // (run, offset in run) of element e, advanced by `istride` per iteration
+  // with one compare instead of a division per element
+  unsigned r, j, dq, dm, run_len;
+  long base, pitch;
+  __device__ __forceinline__ LiveIdx(long i0, long istride, unsigned run_len_,
+                                     long base_, long pitch_)
+      : run_len(run_len_), base(base_), pitch(pitch_) {
+    r = (unsigned)i0 / run_len;
+    j = (unsigned)i0 - r * run_len;
+    dq = (unsigned)istride / run_len;
+    dm = (unsigned)istride - dq * run_len;
+  }
+  __device__ __forceinline__ long at() const {
+    return base + (long)r * pitch + j;
+  }
+  __device__ __forceinline__ void next() {
+    r += dq;
+    j += dm;
+    if (j >= run_len) { j -= run_len; r++; }
+  }
+};
+
+template <bool DECOUPLED, bool SEG = false, bool LIVE = false>
 __device__ __forceinline__ void adam_body(
     float* __restrict__ master, float* __restrict__ grad,
     float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ shadow,
@@ -1756,12 +1783,16 @@ __device__ __forceinline__ void adam_body(
     float eps, float wd, int zero_grad, float* __restrict__ extra_zero,
     long n_extra, const bf16* __restrict__ gsrc, float gscale,
     float* __restrict__ prev, float* __restrict__ sumsq, long i0,
-    long istride, float gmul = 1.f) {
+    long istride, float gmul = 1.f, unsigned run_len = 1, long base = 0,
+    long run_pitch = 0) {
   for (long i = i0; i < n_extra; i += istride) extra_zero[i] = 0.f;
   float t = step_t[0];
   float bc1 = 1.f - __powf(b1, t), bc2 = 1.f - __powf(b2, t);
   float acc = 0.f;
-  for (long i = i0; i < n; i += istride) {
+  LiveIdx li(LIVE ? i0 : 0, LIVE ? istride : 0, run_len, base, run_pitch);
+  for (long e = i0; e < n; e += istride) {
+    const long i = LIVE ? li.at() : e;
+    if (LIVE) li.next();
     float gl = grad[i];
     float g = gsrc != nullptr ? b2f(gsrc[i]) * gscale : gl;
     if (prev != nullptr) {
@@ -1796,15 +1827,19 @@ __device__ __forceinline__ void adam_body(
 }
 
 // NESTEROV: u = μ·mom + g; mom = u; w −= lr·(g + μ·u)  (torch's definition)
-template <bool NESTEROV, bool SEG = false>
+template <bool NESTEROV, bool SEG = false, bool LIVE = false>
 __device__ __forceinline__ void sgd_body(
     float* __restrict__ master, float* __restrict__ grad,
     float* __restrict__ mom, bf16* __restrict__ shadow, long n, float lr,
     float mu, float wd, int zero_grad, const bf16* __restrict__ gsrc,
     float gscale, float* __restrict__ prev, float* __restrict__ sumsq,
-    long i0, long istride, float gmul = 1.f) {
+    long i0, long istride, float gmul = 1.f, unsigned run_len = 1,
+    long base = 0, long run_pitch = 0) {
   float acc = 0.f;
-  for (long i = i0; i < n; i += istride) {
+  LiveIdx li(LIVE ? i0 : 0, LIVE ? istride : 0, run_len, base, run_pitch);
+  for (long e = i0; e < n; e += istride) {
+    const long i = LIVE ? li.at() : e;
+    if (LIVE) li.next();
     float gl = grad[i];
     float g = gsrc != nullptr ? b2f(gsrc[i]) * gscale : gl;
     if (prev != nullptr) {  // fused divergence probe (see adam_body)
@@ -2115,6 +2150,53 @@ __global__ __launch_bounds__(256) void k_adam_step_seg(
                              b2, eps, seg_mul[2 * s + 1], zero_grad, nullptr,
                              0, gsrc, gscale, prev, sumsq,
                              start + threadIdx.x, 256, seg_mul[2 * s]);
+}
+
+// -------------------------------------------------- live-range step ------
+// The unsegmented step over the live part of the flat buffer only: filter
+// taps that only ever meet padding have g = m = v = 0 for good, so without
+// weight decay the update is the identity on them and they are not streamed
+// (docs/KERNELS.md "Live-range step"; the host verifies the precondition
+// when it builds the table).  live[c] = (start, run_len, run_pitch, nruns),
+// int32: chunk c is elements start + r·run_pitch + j, r < nruns,
+// j < run_len.  One workgroup per chunk, so the run geometry is
+// workgroup-uniform.  The body is the full kernels', with wd = 0: a live
+// element gets bitwise what k_adam_step / k_sgd_step(_ex) give it.
+// Scalar accesses as in the full kernels: runs start and end anywhere.
+__global__ __launch_bounds__(256) void k_adam_step_live(
+    float* __restrict__ master, float* __restrict__ grad,
+    float* __restrict__ m, float* __restrict__ v, bf16* __restrict__ shadow,
+    const float* __restrict__ step_t, float lr, float b1, float b2,
+    float eps, int zero_grad, float* __restrict__ extra_zero, long n_extra,
+    const bf16* __restrict__ gsrc, float gscale, float* __restrict__ prev,
+    float* __restrict__ sumsq, const float* __restrict__ lr_table, long T,
+    float* __restrict__ lr_out, const int4* __restrict__ live) {
+  lr = sched_lr(step_t, lr_table, T, lr, lr_out);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n_extra;
+       i += (long)gridDim.x * 256)
+    extra_zero[i] = 0.f;
+  const int4 c = live[blockIdx.x];
+  adam_body<false, false, true>(master, grad, m, v, shadow, step_t,
+                                (long)c.w * c.y, lr, b1, b2, eps, 0.f,
+                                zero_grad, nullptr, 0, gsrc, gscale, prev,
+                                sumsq, threadIdx.x, 256, 1.f, (unsigned)c.y,
+                                c.x, c.z);
+}
+
+template <bool NESTEROV>
+__global__ __launch_bounds__(256) void k_sgd_step_live(
+    float* __restrict__ master, float* __restrict__ grad,
+    float* __restrict__ mom, bf16* __restrict__ shadow, float lr, float mu,
+    int zero_grad, const bf16* __restrict__ gsrc, float gscale,
+    float* __restrict__ prev, float* __restrict__ sumsq,
+    const float* __restrict__ step_t, const float* __restrict__ lr_table,
+    long T, float* __restrict__ lr_out, const int4* __restrict__ live) {
+  lr = sched_lr(step_t, lr_table, T, lr, lr_out);
+  const int4 c = live[blockIdx.x];
+  sgd_body<NESTEROV, false, true>(master, grad, mom, shadow, (long)c.w * c.y,
+                                  lr, mu, 0.f, zero_grad, gsrc, gscale, prev,
+                                  sumsq, threadIdx.x, 256, 1.f,
+                                  (unsigned)c.y, c.x, c.z);
 }
 
 // ------------------------------------------------ dgrad weight transpose ---
@@ -2950,6 +3032,41 @@ void launch_sgd_step_seg(float* master, float* grad, float* mom, void* shadow,
 #define LS(N) k_sgd_step_seg<N><<<nchunks, 256, 0, st>>>( \
     master, grad, mom, (bf16*)shadow, lr, mu, zero_grad, (const bf16*)gsrc, \
     gscale, prev, sumsq, step_t, lr_table, T, lr_out, chunks, seg_mul)
+  if (nesterov) LS(true); else LS(false);
+#undef LS
+  if (prev != nullptr)
+    k_gdiv_finalize<<<1, 1, 0, st>>>(sumsq, divout, 0);
+}
+
+// Live-range forms: the counter bumps are those of the *_ex launchers.
+void launch_adam_step_live(float* master, float* grad, float* m, float* v,
+                           void* shadow, float* step_t, float lr, float b1,
+                           float b2, float eps, int zero_grad,
+                           float* extra_zero, long n_extra, const void* gsrc,
+                           float gscale, float* prev, float* sumsq,
+                           float* divout, const float* lr_table, long T,
+                           float* lr_out, const int* live, int nchunks,
+                           hipStream_t st) {
+  k_inc_step<<<1, 1, 0, st>>>(step_t);
+  k_adam_step_live<<<nchunks, 256, 0, st>>>(
+      master, grad, m, v, (bf16*)shadow, step_t, lr, b1, b2, eps, zero_grad,
+      extra_zero, n_extra, (const bf16*)gsrc, gscale, prev, sumsq, lr_table,
+      T, lr_out, (const int4*)live);
+  if (prev != nullptr)
+    k_gdiv_finalize<<<1, 1, 0, st>>>(sumsq, divout, 0);
+}
+
+void launch_sgd_step_live(float* master, float* grad, float* mom,
+                          void* shadow, float lr, float mu, int zero_grad,
+                          const void* gsrc, float gscale, float* prev,
+                          float* sumsq, float* divout, float* step_t,
+                          const float* lr_table, long T, float* lr_out,
+                          int nesterov, const int* live, int nchunks,
+                          hipStream_t st) {
+  if (lr_table != nullptr) k_inc_step<<<1, 1, 0, st>>>(step_t);
+#define LS(N) k_sgd_step_live<N><<<nchunks, 256, 0, st>>>( \
+    master, grad, mom, (bf16*)shadow, lr, mu, zero_grad, (const bf16*)gsrc, \
+    gscale, prev, sumsq, step_t, lr_table, T, lr_out, (const int4*)live)
   if (nesterov) LS(true); else LS(false);
 #undef LS
   if (prev != nullptr)

@@ -172,6 +172,17 @@ inline bool taps_clipped(const ConvP& p) {
   return p.R != p.Rf || p.S != p.Sf;
 }
 
+// The tap window of a conv's geometry whether or not `p` was clipped: what
+// the window registry (bind.cpp) records.  A tap outside it has an exactly
+// zero weight gradient with clipping off too.
+inline ConvP geometric_taps(ConvP p) {
+  p.r0 = p.s0 = 0;
+  p.R = p.Rf;
+  p.S = p.Sf;
+  p.Kd = p.Rf * p.Sf * p.C;
+  return clip_taps(p);
+}
+
 // ------------------------------------------------------- environment knobs --
 // Every HZ_* knob is read once, as
 //   static const T x = (T)env_long("HZ_...", dflt);
@@ -345,6 +356,25 @@ void launch_sgd_step_seg(float* master, float* grad, float* mom, void* shadow,
                          long T, float* lr_out, int nesterov,
                          const int* chunks, int nchunks, const float* seg_mul,
                          hipStream_t st);
+// Live-range forms (no weight decay): live int32 [nchunks][4] = (start,
+// run_len, run_pitch, nruns), 16-byte aligned; one workgroup per chunk
+// updates elements start + r*run_pitch + j, r < nruns, j < run_len, and
+// nothing else of the flat buffers.
+void launch_adam_step_live(float* master, float* grad, float* m, float* v,
+                           void* shadow, float* step_t, float lr, float b1,
+                           float b2, float eps, int zero_grad,
+                           float* extra_zero, long n_extra, const void* gsrc,
+                           float gscale, float* prev, float* sumsq,
+                           float* divout, const float* lr_table, long T,
+                           float* lr_out, const int* live, int nchunks,
+                           hipStream_t st);
+void launch_sgd_step_live(float* master, float* grad, float* mom,
+                          void* shadow, float lr, float mu, int zero_grad,
+                          const void* gsrc, float gscale, float* prev,
+                          float* sumsq, float* divout, float* step_t,
+                          const float* lr_table, long T, float* lr_out,
+                          int nesterov, const int* live, int nchunks,
+                          hipStream_t st);
 
 // elem_kernels.hip: layout, probes, input pipeline
 void launch_permute_krsc_rsck(const void* src, void* dst, const int* meta,
