@@ -62,6 +62,16 @@ bool g_wgrad_tr = env_long("HZ_WGRAD_TR", 1) != 0;
 void set_wgrad_tr(bool on) { g_wgrad_tr = on; }
 bool wgrad_tr_enabled() { return g_wgrad_tr; }
 
+// Classifier tail (elem_kernels.hip, launch_linear_* / launch_ce_*): runtime
+// switches so one process can run both dispatches (tests, A/B timing).
+// HZ_LINEAR_BWD_FUSED: dx, dW and db in one launch (Out <= 16, B <= 128);
+// HZ_CE_STORE: the single-workgroup loss kernel stores the loss, no fill.
+// Both default on; deterministic mode always keeps the former kernels.
+void set_linear_bwd_fused(bool on) { set_kernels_linear_bwd_fused(on ? 1 : 0); }
+bool linear_bwd_fused_enabled() { return kernels_linear_bwd_fused() != 0; }
+void set_ce_store(bool on) { set_kernels_ce_store(on ? 1 : 0); }
+bool ce_store_enabled() { return kernels_ce_store() != 0; }
+
 // Tap window (launch.h, clip_taps): forward, dgrad and wgrad skip the filter
 // taps that only ever meet padding.  HZ_TAP_CLIP (read at load, default on);
 // off = every conv walks its whole filter, kept for A/B timing and as the
@@ -962,7 +972,9 @@ std::vector<Tensor> cross_entropy_fwd_bwd(Tensor logits, Tensor target) {
   check_f32(logits, "logits");
   TORCH_CHECK(target.scalar_type() == torch::kLong && target.is_contiguous());
   int B = (int)logits.size(0), NC = (int)logits.size(1);
-  Tensor loss = at::zeros({}, logits.options());
+  // a kernel that stores the loss needs no zeroed scalar: no fill dispatch
+  Tensor loss = ce_loss_stored(B) ? at::empty({}, logits.options())
+                                  : at::zeros({}, logits.options());
   Tensor dlogits = at::empty({B, NC}, logits.options());
   launch_ce_fwd_bwd(logits.data_ptr<float>(), target.data_ptr<long>(),
                     loss.data_ptr<float>(), dlogits.data_ptr<float>(), B, NC,
@@ -979,7 +991,9 @@ std::vector<Tensor> cross_entropy_ls_fwd_bwd(Tensor logits, Tensor target,
   check_f32(logits, "logits");
   TORCH_CHECK(target.scalar_type() == torch::kLong && target.is_contiguous());
   int B = (int)logits.size(0), NC = (int)logits.size(1);
-  Tensor loss = at::zeros({}, logits.options());
+  // a kernel that stores the loss needs no zeroed scalar: no fill dispatch
+  Tensor loss = ce_loss_stored(B) ? at::empty({}, logits.options())
+                                  : at::zeros({}, logits.options());
   Tensor dlogits = at::empty({B, NC}, logits.options());
   launch_ce_ls_fwd_bwd(logits.data_ptr<float>(), target.data_ptr<long>(),
                        loss.data_ptr<float>(), dlogits.data_ptr<float>(), B,
@@ -1643,6 +1657,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_dgrad_only", &conv_dgrad_only);
   m.def("set_dgrad_krsc", &set_dgrad_krsc);
   m.def("dgrad_krsc_enabled", &dgrad_krsc_enabled);
+  m.def("set_linear_bwd_fused", &set_linear_bwd_fused);
+  m.def("linear_bwd_fused_enabled", &linear_bwd_fused_enabled);
+  m.def("set_ce_store", &set_ce_store);
+  m.def("ce_store_enabled", &ce_store_enabled);
   m.def("set_wgrad_tr", &set_wgrad_tr);
   m.def("wgrad_tr_enabled", &wgrad_tr_enabled);
   m.def("set_tap_clip", &set_tap_clip);

@@ -1463,11 +1463,21 @@ __global__ __launch_bounds__(256) void k_avgpool_bwd(
 }
 
 // ------------------------------------------------------------- classifier --
+// The kernels marked HZ_NO_PK_F32 are compiled without packed-f32 VALU ops (a
+// device-side target feature; the host pass does not know it).
+#if defined(__HIP_DEVICE_COMPILE__)
+#define HZ_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define HZ_NO_PK_F32
+#endif
+
 // Small fc: x[B,In] bf16 · w[Out,In] bf16 + b[Out] f32 -> logits[B,Out] f32.
 // One wave per sample row: the wave loads x[b,:] as vec8 per lane (In ≤ 512
 // in one shot), then per output j the w row streams through all lanes and
 // the dot product closes with a wave shuffle reduction — every load is a
 // coalesced 16 B vector (the scalar-load version measured 83 µs; this ~6 µs).
+// (Taking the outputs as a group — all partial sums first, one xor tree for
+// the group — measured 14.0 µs against 8.6: docs/STATUS.md, negative results.)
 __global__ __launch_bounds__(256) void k_linear_fwd(
     const bf16* __restrict__ x, const bf16* __restrict__ w,
     const float* __restrict__ b, float* __restrict__ y, int B, int In,
@@ -1560,6 +1570,114 @@ __global__ __launch_bounds__(256) void k_linear_bwd_dw_small(
   if (blockIdx.x == 0 && tid < Out && db != nullptr) {
     float sb = 0.f;
     for (int bi = 0; bi < B; bi++) sb += dys[bi * OUTN + tid];
+    db[tid] = accum ? db[tid] + sb : sb;
+  }
+}
+
+// dx, dW and db of the classifier shape (Out ≤ 16, B ≤ 128) in one launch.
+// A block owns LBS_COLS input columns; its 256 threads are LBS_COLS columns ×
+// LBS_ROWL row-lanes, row-lane r walking the batch rows r, r+8, ...  dy is
+// staged once as [B][16] (zero-padded) and the block's w columns as
+// [16][LBS_COLS] f32, so each x[b][t] is loaded once (it feeds dW) and each
+// w[j][t] once (it feeds dx).  The x loads of a thread go out eight at a time
+// before any of them is used.
+//   dx[b][t]: the fmaf chain over j of k_linear_bwd_dx — bitwise its result.
+//   dW[j][t]: the 8 row-lane partials meet in a fixed order — the two
+//     row-lanes of a wave by one xor-32 shuffle, the 4 waves through LDS,
+//     summed 0..3.  db likewise from 8 LDS partials (block 0).  No atomics:
+//     two runs agree bitwise.
+// 16 workgroups at In = 512 against the 2 of k_linear_bwd_dw_small, whose
+// threads each walk all B rows with the load inside the dependent loop.
+constexpr int LBS_COLS = 32;
+constexpr int LBS_ROWL = 8;
+HZ_NO_PK_F32 __global__ __launch_bounds__(256) void k_linear_bwd_small(
+    const float* __restrict__ dy, const bf16* __restrict__ x,
+    const bf16* __restrict__ w, bf16* __restrict__ dx,
+    float* __restrict__ dw, float* __restrict__ db, int B, int In, int Out,
+    int accum) {
+  constexpr int OUTN = 16;
+  __shared__ __attribute__((aligned(16))) float dys[128 * OUTN];  // [B][16]
+  __shared__ float ws[OUTN * LBS_COLS];                   // [16][cols]
+  __shared__ float part[4 * OUTN * LBS_COLS];             // [wave][16][cols]
+  __shared__ float dbp[LBS_ROWL * OUTN];                  // [row-lane][16]
+  const int tid = threadIdx.x;
+  const int c = tid & (LBS_COLS - 1), r = tid >> 5;
+  const int t0 = blockIdx.x * LBS_COLS;
+  const int t = t0 + c;
+  const bool live = t < In;
+  for (int i = tid; i < B * OUTN; i += 256) {
+    int j = i & (OUTN - 1);
+    dys[i] = j < Out ? dy[(i >> 4) * Out + j] : 0.f;
+  }
+  if (dx != nullptr)
+    for (int i = tid; i < OUTN * LBS_COLS; i += 256) {
+      int j = i >> 5, tt = t0 + (i & (LBS_COLS - 1));
+      ws[i] = (j < Out && tt < In) ? b2f(w[(long)j * In + tt]) : 0.f;
+    }
+  __syncthreads();
+  float wv[OUTN];
+  if (dx != nullptr) {
+#pragma unroll
+    for (int j = 0; j < OUTN; j++) wv[j] = ws[j * LBS_COLS + c];
+  }
+  float s[OUTN];
+#pragma unroll
+  for (int j = 0; j < OUTN; j++) s[j] = 0.f;
+  for (int b0 = 0; b0 < B; b0 += 8 * LBS_ROWL) {
+    float xv[8];
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      int bi = b0 + r + i * LBS_ROWL;
+      xv[i] = (live && bi < B) ? b2f(x[(long)bi * In + t]) : 0.f;
+    }
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+      int bi = b0 + r + i * LBS_ROWL;
+      if (bi < B) {  // bi ≤ 127: inside dys
+        float d[OUTN];
+#pragma unroll
+        for (int j = 0; j < OUTN; j++) d[j] = dys[bi * OUTN + j];
+#pragma unroll
+        for (int j = 0; j < OUTN; j++) s[j] = fmaf(d[j], xv[i], s[j]);
+        if (dx != nullptr && live) {
+          float a = 0.f;
+#pragma unroll
+          for (int j = 0; j < OUTN; j++)
+            if (j < Out) a = fmaf(d[j], wv[j], a);
+          dx[(long)bi * In + t] = f2b(a);
+        }
+      }
+    }
+  }
+  // row-lanes r and r+1 of a wave, then the waves through LDS
+#pragma unroll
+  for (int j = 0; j < OUTN; j++) s[j] += __shfl_xor(s[j], 32, 64);
+  if ((tid & 32) == 0) {
+#pragma unroll
+    for (int j = 0; j < OUTN; j++)
+      part[((tid >> 6) * OUTN + j) * LBS_COLS + c] = s[j];
+  }
+  if (db != nullptr && blockIdx.x == 0 && tid < LBS_ROWL * OUTN) {
+    int rr = tid >> 4, j = tid & (OUTN - 1);
+    float sb = 0.f;
+    for (int bi = rr; bi < B; bi += LBS_ROWL) sb += dys[bi * OUTN + j];
+    dbp[tid] = sb;
+  }
+  __syncthreads();
+  for (int i = tid; i < OUTN * LBS_COLS; i += 256) {
+    int j = i >> 5, tt = t0 + (i & (LBS_COLS - 1));
+    if (j < Out && tt < In) {
+      float v = part[i];
+#pragma unroll
+      for (int wv_ = 1; wv_ < 4; wv_++) v += part[wv_ * OUTN * LBS_COLS + i];
+      long o = (long)j * In + tt;
+      dw[o] = accum ? dw[o] + v : v;
+    }
+  }
+  if (db != nullptr && blockIdx.x == 0 && tid < Out) {
+    float sb = dbp[tid];
+#pragma unroll
+    for (int rr = 1; rr < LBS_ROWL; rr++) sb += dbp[rr * OUTN + tid];
     db[tid] = accum ? db[tid] + sb : sb;
   }
 }
@@ -1692,6 +1810,54 @@ __device__ __forceinline__ void ce_body(
   for (int b = b0; b < B; b += bstride)
     atomicAdd(loss, ce_row<LS>(logits + (long)b * NC, (int)target[b], B, NC,
                                eps, dlogits + (long)b * NC));
+}
+
+// Single-workgroup form (B ≤ 256, one row per thread): the loss is STORED,
+// so the host hands in an uninitialised scalar and no fill runs in front.
+// The sum is spelled out in the order ce_body's atomicAdd takes within one
+// workgroup: the compiler turns that uniform-address atomic into a serial
+// lane-ascending sum per wave and one atomic per wave, so here lane 0 of
+// each wave adds its wave's rows in lane order and thread 0 adds the wave
+// sums in wave order.  Reassociation is off for these sums (the build is
+// -ffast-math); no atomics, so the loss is also repeatable.
+template <bool LS>
+__device__ __forceinline__ void ce_one_body(
+    const float* __restrict__ logits, const long* __restrict__ target,
+    float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC,
+    float eps) {
+#pragma clang fp reassociate(off)
+  __shared__ float rowv[256];
+  __shared__ float wsum[4];
+  const int b = threadIdx.x;
+  if (b < B)
+    rowv[b] = ce_row<LS>(logits + (long)b * NC, (int)target[b], B, NC, eps,
+                         dlogits + (long)b * NC);
+  __syncthreads();
+  if ((b & 63) == 0 && b < B) {
+    const int n = min(64, B - b);
+    float acc = rowv[b];
+    for (int i = 1; i < n; i++) acc = rowv[b + i] + acc;
+    wsum[b >> 6] = acc;
+  }
+  __syncthreads();
+  if (b == 0) {
+    float s = wsum[0];
+    for (int i = 1; i * 64 < B; i++) s += wsum[i];
+    loss[0] = s;
+  }
+}
+
+HZ_NO_PK_F32 __global__ __launch_bounds__(256) void k_ce_fwd_bwd_one(
+    const float* __restrict__ logits, const long* __restrict__ target,
+    float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC) {
+  ce_one_body<false>(logits, target, loss, dlogits, B, NC, 0.f);
+}
+
+HZ_NO_PK_F32 __global__ __launch_bounds__(256) void k_ce_ls_fwd_bwd_one(
+    const float* __restrict__ logits, const long* __restrict__ target,
+    float* __restrict__ loss, float* __restrict__ dlogits, int B, int NC,
+    float eps) {
+  ce_one_body<true>(logits, target, loss, dlogits, B, NC, eps);
 }
 
 __global__ __launch_bounds__(256) void k_ce_fwd_bwd_det(
@@ -2867,6 +3033,15 @@ void launch_avgpool_bwd(const void* dy, void* dx, int Nb, int HW, int C,
                                                         (bf16*)dx, Nb, HW, C);
 }
 
+// Classifier-tail switches (read at load; docs/TUNING.md).  Each keeps the
+// former kernels for A/B timing and as the tests' reference.
+static int g_linear_bwd_fused = (int)env_long("HZ_LINEAR_BWD_FUSED", 1);
+static int g_ce_store = (int)env_long("HZ_CE_STORE", 1);
+void set_kernels_linear_bwd_fused(int on) { g_linear_bwd_fused = on; }
+int kernels_linear_bwd_fused() { return g_linear_bwd_fused; }
+void set_kernels_ce_store(int on) { g_ce_store = on; }
+int kernels_ce_store() { return g_ce_store; }
+
 void launch_linear_fwd(const void* x, const void* w, const float* b, float* y,
                        int B, int In, int Out, hipStream_t st) {
   k_linear_fwd<<<(B + 3) / 4, 256, 0, st>>>((const bf16*)x, (const bf16*)w,
@@ -2876,6 +3051,13 @@ void launch_linear_fwd(const void* x, const void* w, const float* b, float* y,
 void launch_linear_bwd(const float* dy, const void* x, const void* w,
                        void* dx, float* dw, float* db, int B, int In, int Out,
                        int accum, hipStream_t st) {
+  // deterministic mode keeps the two-kernel dispatch
+  if (g_linear_bwd_fused && !g_det_kernels && Out <= 16 && B <= 128) {
+    k_linear_bwd_small<<<(In + LBS_COLS - 1) / LBS_COLS, 256, 0, st>>>(
+        dy, (const bf16*)x, (const bf16*)w, (bf16*)dx, dw, db, B, In, Out,
+        accum);
+    return;
+  }
   if (dx)
     k_linear_bwd_dx<<<gsz((long)B * In), 256, 0, st>>>(dy, (const bf16*)w,
                                                        (bf16*)dx, B, In, Out);
@@ -2901,10 +3083,20 @@ void launch_linear_bwd(const float* dy, const void* x, const void* w,
         dy, (const bf16*)x, dw, db, B, In, Out, accum);
 }
 
+// 1: the launch for batch B stores the loss (single workgroup, B ≤ 256), so
+// `loss` may be uninitialised; 0: it adds into loss[0], which must be zero
+// (the _det kernels store too, and are handed a zeroed scalar all the same).
+int ce_loss_stored(int B) {
+  return g_ce_store && !g_det_kernels && gsz(B) == 1 && B <= 256;
+}
+
 void launch_ce_fwd_bwd(const float* logits, const long* target, float* loss,
                        float* dlogits, int B, int NC, hipStream_t st) {
   if (g_det_kernels)
     k_ce_fwd_bwd_det<<<1, 256, 0, st>>>(logits, target, loss, dlogits, B,
+                                        NC);
+  else if (ce_loss_stored(B))
+    k_ce_fwd_bwd_one<<<1, 256, 0, st>>>(logits, target, loss, dlogits, B,
                                         NC);
   else
     k_ce_fwd_bwd<<<gsz(B), 256, 0, st>>>(logits, target, loss, dlogits, B,
@@ -2916,6 +3108,9 @@ void launch_ce_ls_fwd_bwd(const float* logits, const long* target,
                           float eps, hipStream_t st) {
   if (g_det_kernels)
     k_ce_ls_fwd_bwd_det<<<1, 256, 0, st>>>(logits, target, loss, dlogits, B,
+                                           NC, eps);
+  else if (ce_loss_stored(B))
+    k_ce_ls_fwd_bwd_one<<<1, 256, 0, st>>>(logits, target, loss, dlogits, B,
                                            NC, eps);
   else
     k_ce_ls_fwd_bwd<<<gsz(B), 256, 0, st>>>(logits, target, loss, dlogits, B,

@@ -226,6 +226,14 @@ int kernels_bn_owner();
 void bn_owner_launch_counts(long* fwd, long* bwd);
 int bn_owner_fwd_pick(long M, int C, int lpr_req);
 int bn_owner_bwd_pick(long M, int C, int lpr_req);
+// classifier tail: fused one-launch backward (k_linear_bwd_small) and the
+// single-workgroup CE that stores its loss
+void set_kernels_linear_bwd_fused(int on);
+int kernels_linear_bwd_fused();
+void set_kernels_ce_store(int on);
+int kernels_ce_store();
+// 1 when launch_ce_*_fwd_bwd at batch B stores the loss (no zeroed scalar)
+int ce_loss_stored(int B);
 
 // elem_kernels.hip: BatchNorm
 void launch_bn_apply(const void* x, const void* res, void* y,
