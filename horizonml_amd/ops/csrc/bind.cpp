@@ -72,6 +72,20 @@ bool linear_bwd_fused_enabled() { return kernels_linear_bwd_fused() != 0; }
 void set_ce_store(bool on) { set_kernels_ce_store(on ? 1 : 0); }
 bool ce_store_enabled() { return kernels_ce_store() != 0; }
 
+// Wide head (head_kernels.hip): the MFMA linear kernels at Out > 16
+// (HZ_LINEAR_WIDE) and the wave-per-row CE at NC > 32 (HZ_CE_WIDE).  Both
+// default on; off = the former kernels at those shapes.
+void set_linear_wide(bool on) { set_kernels_linear_wide(on ? 1 : 0); }
+bool linear_wide_enabled() { return kernels_linear_wide() != 0; }
+void set_ce_wide(bool on) { set_kernels_ce_wide(on ? 1 : 0); }
+bool ce_wide_enabled() { return kernels_ce_wide() != 0; }
+// (forward, backward) wide-head linear launches so far in this process.
+std::vector<int64_t> linear_wide_launches() {
+  long f = 0, b = 0;
+  linear_wide_launch_counts(&f, &b);
+  return {(int64_t)f, (int64_t)b};
+}
+
 // Tap window (launch.h, clip_taps): forward, dgrad and wgrad skip the filter
 // taps that only ever meet padding.  HZ_TAP_CLIP (read at load, default on);
 // off = every conv walks its whole filter, kept for A/B timing and as the
@@ -973,8 +987,8 @@ std::vector<Tensor> cross_entropy_fwd_bwd(Tensor logits, Tensor target) {
   TORCH_CHECK(target.scalar_type() == torch::kLong && target.is_contiguous());
   int B = (int)logits.size(0), NC = (int)logits.size(1);
   // a kernel that stores the loss needs no zeroed scalar: no fill dispatch
-  Tensor loss = ce_loss_stored(B) ? at::empty({}, logits.options())
-                                  : at::zeros({}, logits.options());
+  Tensor loss = ce_loss_stored(B, NC) ? at::empty({}, logits.options())
+                                      : at::zeros({}, logits.options());
   Tensor dlogits = at::empty({B, NC}, logits.options());
   launch_ce_fwd_bwd(logits.data_ptr<float>(), target.data_ptr<long>(),
                     loss.data_ptr<float>(), dlogits.data_ptr<float>(), B, NC,
@@ -992,8 +1006,8 @@ std::vector<Tensor> cross_entropy_ls_fwd_bwd(Tensor logits, Tensor target,
   TORCH_CHECK(target.scalar_type() == torch::kLong && target.is_contiguous());
   int B = (int)logits.size(0), NC = (int)logits.size(1);
   // a kernel that stores the loss needs no zeroed scalar: no fill dispatch
-  Tensor loss = ce_loss_stored(B) ? at::empty({}, logits.options())
-                                  : at::zeros({}, logits.options());
+  Tensor loss = ce_loss_stored(B, NC) ? at::empty({}, logits.options())
+                                      : at::zeros({}, logits.options());
   Tensor dlogits = at::empty({B, NC}, logits.options());
   launch_ce_ls_fwd_bwd(logits.data_ptr<float>(), target.data_ptr<long>(),
                        loss.data_ptr<float>(), dlogits.data_ptr<float>(), B,
@@ -1661,6 +1675,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("linear_bwd_fused_enabled", &linear_bwd_fused_enabled);
   m.def("set_ce_store", &set_ce_store);
   m.def("ce_store_enabled", &ce_store_enabled);
+  m.def("set_linear_wide", &set_linear_wide);
+  m.def("linear_wide_enabled", &linear_wide_enabled);
+  m.def("set_ce_wide", &set_ce_wide);
+  m.def("ce_wide_enabled", &ce_wide_enabled);
+  m.def("linear_wide_launches", &linear_wide_launches);
   m.def("set_wgrad_tr", &set_wgrad_tr);
   m.def("wgrad_tr_enabled", &wgrad_tr_enabled);
   m.def("set_tap_clip", &set_tap_clip);

@@ -3042,8 +3042,39 @@ int kernels_linear_bwd_fused() { return g_linear_bwd_fused; }
 void set_kernels_ce_store(int on) { g_ce_store = on; }
 int kernels_ce_store() { return g_ce_store; }
 
+// Wide head (head_kernels.hip; docs/KERNELS.md, "Wide head").  Both switches
+// default on and are read at load; off launches the former kernels.  The
+// linear kernels have no atomics and serve deterministic mode too; the wide
+// CE adds into the loss scalar, so deterministic mode keeps its _det kernels.
+static int g_linear_wide = (int)env_long("HZ_LINEAR_WIDE", 1);
+static int g_ce_wide = (int)env_long("HZ_CE_WIDE", 1);
+static long g_wide_fwd_launches = 0, g_wide_bwd_launches = 0;
+void set_kernels_linear_wide(int on) { g_linear_wide = on; }
+int kernels_linear_wide() { return g_linear_wide; }
+void set_kernels_ce_wide(int on) { g_ce_wide = on; }
+int kernels_ce_wide() { return g_ce_wide; }
+void linear_wide_launch_counts(long* fwd, long* bwd) {
+  *fwd = g_wide_fwd_launches;
+  *bwd = g_wide_bwd_launches;
+}
+
+// the head kernels read x and w as 16-byte vectors of 8 bf16
+static bool linear_wide_pick(const void* x, const void* w, int In, int Out) {
+  return g_linear_wide && Out > 16 && In % 8 == 0 &&
+         (((size_t)x | (size_t)w) & 15) == 0;
+}
+
+static bool ce_wide_pick(int NC) {
+  return g_ce_wide && !g_det_kernels && NC > 32 && NC <= CE_WIDE_MAX_NC;
+}
+
 void launch_linear_fwd(const void* x, const void* w, const float* b, float* y,
                        int B, int In, int Out, hipStream_t st) {
+  if (linear_wide_pick(x, w, In, Out)) {
+    launch_head_fwd(x, w, b, y, B, In, Out, st);
+    g_wide_fwd_launches++;
+    return;
+  }
   k_linear_fwd<<<(B + 3) / 4, 256, 0, st>>>((const bf16*)x, (const bf16*)w,
                                             b, y, B, In, Out);
 }
@@ -3051,6 +3082,11 @@ void launch_linear_fwd(const void* x, const void* w, const float* b, float* y,
 void launch_linear_bwd(const float* dy, const void* x, const void* w,
                        void* dx, float* dw, float* db, int B, int In, int Out,
                        int accum, hipStream_t st) {
+  if (linear_wide_pick(x, w, In, Out)) {
+    launch_head_bwd(dy, x, w, dx, dw, db, B, In, Out, accum, st);
+    g_wide_bwd_launches++;
+    return;
+  }
   // deterministic mode keeps the two-kernel dispatch
   if (g_linear_bwd_fused && !g_det_kernels && Out <= 16 && B <= 128) {
     k_linear_bwd_small<<<(In + LBS_COLS - 1) / LBS_COLS, 256, 0, st>>>(
@@ -3086,7 +3122,8 @@ void launch_linear_bwd(const float* dy, const void* x, const void* w,
 // 1: the launch for batch B stores the loss (single workgroup, B ≤ 256), so
 // `loss` may be uninitialised; 0: it adds into loss[0], which must be zero
 // (the _det kernels store too, and are handed a zeroed scalar all the same).
-int ce_loss_stored(int B) {
+int ce_loss_stored(int B, int NC) {
+  if (ce_wide_pick(NC)) return 0;  // k_ce_wide adds into the scalar
   return g_ce_store && !g_det_kernels && gsz(B) == 1 && B <= 256;
 }
 
@@ -3095,7 +3132,9 @@ void launch_ce_fwd_bwd(const float* logits, const long* target, float* loss,
   if (g_det_kernels)
     k_ce_fwd_bwd_det<<<1, 256, 0, st>>>(logits, target, loss, dlogits, B,
                                         NC);
-  else if (ce_loss_stored(B))
+  else if (ce_wide_pick(NC))
+    launch_ce_wide(logits, target, loss, dlogits, B, NC, 0.f, 0, st);
+  else if (ce_loss_stored(B, NC))
     k_ce_fwd_bwd_one<<<1, 256, 0, st>>>(logits, target, loss, dlogits, B,
                                         NC);
   else
@@ -3109,7 +3148,9 @@ void launch_ce_ls_fwd_bwd(const float* logits, const long* target,
   if (g_det_kernels)
     k_ce_ls_fwd_bwd_det<<<1, 256, 0, st>>>(logits, target, loss, dlogits, B,
                                            NC, eps);
-  else if (ce_loss_stored(B))
+  else if (ce_wide_pick(NC))
+    launch_ce_wide(logits, target, loss, dlogits, B, NC, eps, 1, st);
+  else if (ce_loss_stored(B, NC))
     k_ce_ls_fwd_bwd_one<<<1, 256, 0, st>>>(logits, target, loss, dlogits, B,
                                            NC, eps);
   else

@@ -93,6 +93,10 @@ static_assert(std::is_trivially_copyable_v<WgradBatchArgs> &&
                   std::is_trivially_copyable_v<WredBatchArgs>,
               "batched wgrad task tables are copied into the kernarg segment");
 
+// Widest row of the wave-per-row CE: four f32 rows fill the 64 KB of LDS a
+// kernel gets without opting in to more.
+constexpr int CE_WIDE_MAX_NC = 4096;
+
 // Weight layout handed to launch_conv_dgrad.
 enum DgradWLayout { DGRAD_W_RSCK = 0, DGRAD_W_KRSC = 1 };
 
@@ -232,8 +236,15 @@ void set_kernels_linear_bwd_fused(int on);
 int kernels_linear_bwd_fused();
 void set_kernels_ce_store(int on);
 int kernels_ce_store();
-// 1 when launch_ce_*_fwd_bwd at batch B stores the loss (no zeroed scalar)
-int ce_loss_stored(int B);
+// 1 when launch_ce_*_fwd_bwd at [B, NC] stores the loss (no zeroed scalar)
+int ce_loss_stored(int B, int NC);
+// wide head (head_kernels.hip): MFMA linear at Out > 16, wave-per-row CE at
+// 32 < NC <= CE_WIDE_MAX_NC; off = the former kernels at those shapes
+void set_kernels_linear_wide(int on);
+int kernels_linear_wide();
+void set_kernels_ce_wide(int on);
+int kernels_ce_wide();
+void linear_wide_launch_counts(long* fwd, long* bwd);
 
 // elem_kernels.hip: BatchNorm
 void launch_bn_apply(const void* x, const void* res, void* y,
@@ -312,6 +323,18 @@ void launch_ce_fwd_bwd(const float* logits, const long* target, float* loss,
 void launch_ce_ls_fwd_bwd(const float* logits, const long* target,
                           float* loss, float* dlogits, int B, int NC,
                           float eps, hipStream_t st);
+
+// head_kernels.hip: called by the launch_linear_* / launch_ce_* dispatch of
+// elem_kernels.hip only.  In % 8 == 0; x and w 16-byte aligned.
+void launch_head_fwd(const void* x, const void* w, const float* b, float* y,
+                     int B, int In, int Out, hipStream_t st);
+void launch_head_bwd(const float* dy, const void* x, const void* w, void* dx,
+                     float* dw, float* db, int B, int In, int Out, int accum,
+                     hipStream_t st);
+// loss[0] must be zero; ls != 0 is the label-smoothed form
+void launch_ce_wide(const float* logits, const long* target, float* loss,
+                    float* dlogits, int B, int NC, float eps, int ls,
+                    hipStream_t st);
 
 // elem_kernels.hip: optimizers.  step_t is the device step counter; the
 // Adam launchers (and SGD with a table) increment it before the update.

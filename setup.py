@@ -20,9 +20,15 @@ CSRC = os.path.join(ROOT, "horizonml_amd", "ops", "csrc")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
-HIP_SOURCES = ["conv_kernels.hip", "elem_kernels.hip"]
+HIP_SOURCES = ["conv_kernels.hip", "elem_kernels.hip", "head_kernels.hip"]
 HIPCC_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
                "-ffast-math"]
+# per-file additions: head_kernels.hip is compiled without packed-f32 VALU
+# ops as a whole (elem_kernels.hip marks single kernels, HZ_NO_PK_F32)
+HIPCC_FILE_FLAGS = {
+    "head_kernels.hip": ["-Xclang", "-target-feature", "-Xclang",
+                         "-packed-fp32-ops"],
+}
 
 
 # every translation unit (bind.cpp included) sees the csrc headers: a change
@@ -39,7 +45,8 @@ def compile_hip_objects():
                 or any(os.path.getmtime(obj_path) < os.path.getmtime(dep)
                        for dep in [src_path] + HEADERS)):
             cmd = [os.path.join(ROCM, "bin", "hipcc"), "-c", src_path,
-                   "-o", obj_path] + HIPCC_FLAGS
+                   "-o", obj_path] + HIPCC_FLAGS \
+                + HIPCC_FILE_FLAGS.get(src, [])
             print("[hipcc]", " ".join(cmd), flush=True)
             subprocess.check_call(cmd)
         objs.append(obj_path)
