@@ -34,7 +34,8 @@ import torch
 import torch.nn as nn
 
 from .. import ops as _ops
-from ..models.layers import ConvBNAct, DepthwiseConvBNAct, Linear
+from ..models.layers import (ConvBNAct, DepthwiseConvBNAct,
+                             GroupedConvBNAct, Linear)
 
 
 SEG_CHUNK = 4096  # elements per chunk = per workgroup of the *_seg kernels
@@ -241,7 +242,8 @@ class FlatParamManager:
         # wire bf16 shadow views into the modules; collect conv RSCK metadata
         convs = []
         for m in model.modules():
-            if isinstance(m, (ConvBNAct, Linear, DepthwiseConvBNAct)):
+            if isinstance(m, (ConvBNAct, Linear, DepthwiseConvBNAct,
+                              GroupedConvBNAct)):
                 woff, wn = self.slices[id(m.weight)]
                 m.weight_bf16 = self.shadow[woff:woff + wn].view(
                     m.weight.shape)

@@ -1,5 +1,7 @@
-from .resnet import ResNet, BasicBlock, Bottleneck, resnet18, resnet34, resnet50, build_model  # noqa: F401
+from .resnet import (ResNet, BasicBlock, Bottleneck, resnet18, resnet34,  # noqa: F401
+                     resnet50, resnext50_32x4d, build_model)
 from .mobilenet import mobilenet_v2  # noqa: F401
 from .partition import partition_model, partition_units, split_counts  # noqa: F401
-from .layers import (ConvBNAct, DepthwiseConvBNAct, Linear, GlobalAvgPool,  # noqa: F401
-                     MaxPool2d3x3s2, refresh_all_shadows)
+from .layers import (ConvBNAct, DepthwiseConvBNAct, GroupedConvBNAct,  # noqa: F401
+                     Linear, GlobalAvgPool, MaxPool2d3x3s2,
+                     refresh_all_shadows)

@@ -191,6 +191,97 @@ class DepthwiseConvBNAct(nn.Module):
         return y
 
 
+class GroupedConvBNAct(nn.Module):
+    """Fused grouped Conv2d (1 < groups < C) + BatchNorm2d [+ residual add]
+    [+ act] — the ResNeXt bottleneck's 3x3, on the block-diagonal MFMA
+    kernels of ``grouped_kernels.hip``.  Weight layout [K, R, S, Cg]
+    (out-ch, kh, kw, in-ch within the group).
+
+    A class of its own, not a ``ConvBNAct``: the flat engine's stats arena,
+    RSCK metadata and tap-window registry are keyed on ``ConvBNAct`` and a
+    [K, R, S, C] weight, and the residual blocks' fused path on
+    ``type(m) is ConvBNAct``.  The GPU kernels serve in_ch == out_ch with 4,
+    8, 16 or 32 channels per group, a 1x1 or 3x3 filter and stride 1 or 2;
+    other shapes run on the CPU path only and are refused on the GPU."""
+
+    def __init__(self, in_ch: int, out_ch: int, kernel_size: int = 3,
+                 stride: int = 1, padding: Optional[int] = None,
+                 groups: int = 32, act=True, eps: float = 1e-5,
+                 momentum: float = 0.1):
+        super().__init__()
+        if padding is None:
+            padding = kernel_size // 2
+        if groups < 1 or in_ch % groups or out_ch % groups:
+            raise ValueError(f"groups={groups} must divide in_ch={in_ch} "
+                             f"and out_ch={out_ch}")
+        self.in_ch, self.out_ch, self.groups = in_ch, out_ch, groups
+        self.kernel_size, self.stride, self.padding = (kernel_size, stride,
+                                                       padding)
+        self.act = ConvBNAct.ACT[act] if not isinstance(act, int) else act
+        self.eps, self.momentum = eps, momentum
+        self.weight = nn.Parameter(
+            torch.empty(out_ch, kernel_size, kernel_size, in_ch // groups))
+        self.bn_weight = nn.Parameter(torch.ones(out_ch))
+        self.bn_bias = nn.Parameter(torch.zeros(out_ch))
+        self.register_buffer("running_mean", torch.zeros(out_ch))
+        self.register_buffer("running_var", torch.ones(out_ch))
+        self.register_buffer("num_batches_tracked",
+                             torch.tensor(0, dtype=torch.long))
+        self.register_buffer("weight_bf16", torch.empty(0), persistent=False)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        # Kaiming-normal fan_out, as ConvBNAct (torch's fan_out of a grouped
+        # conv weight [K, Cg, R, S] is K*R*S as well)
+        fan_out = self.kernel_size * self.kernel_size * self.out_ch
+        with torch.no_grad():
+            self.weight.normal_(0, math.sqrt(2.0 / fan_out))
+
+    def extra_repr(self):
+        return (f"{self.in_ch}, {self.out_ch}, k={self.kernel_size}, "
+                f"s={self.stride}, p={self.padding}, groups={self.groups}, "
+                f"act={self.act}")
+
+    def refresh_shadow(self):
+        if getattr(self, "_managed", False):
+            return
+        with torch.no_grad():
+            if (self.weight_bf16.shape == self.weight.shape
+                    and self.weight_bf16.device == self.weight.device):
+                self.weight_bf16.copy_(self.weight.detach())
+            else:
+                self.weight_bf16 = self.weight.detach() \
+                    .to(torch.bfloat16).contiguous()
+
+    def _shadow(self) -> torch.Tensor:
+        if getattr(self, "_managed", False):
+            return self.weight_bf16
+        if (self.weight_bf16.numel() != self.weight.numel()
+                or self.weight_bf16.device != self.weight.device):
+            self.refresh_shadow()
+        return self.weight_bf16
+
+    def forward(self, x: torch.Tensor,
+                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if _use_hip(x):
+            from . import _functional_gpu as FG
+            return FG.grouped_conv_bn_act(x, self, residual)
+        # CPU reference path: [K,R,S,Cg] -> torch's [K,Cg,R,S]
+        w = self.weight.permute(0, 3, 1, 2)
+        y = F.conv2d(x, w, None, stride=self.stride, padding=self.padding,
+                     groups=self.groups)
+        y = F.batch_norm(y, self.running_mean, self.running_var,
+                         self.bn_weight, self.bn_bias, self.training,
+                         self.momentum, self.eps)
+        if residual is not None:
+            y = y + residual
+        if self.act == 1:
+            y = F.relu(y)
+        elif self.act == 2:
+            y = F.hardtanh(y, 0.0, 6.0)
+        return y
+
+
 class MaxPool2d3x3s2(nn.Module):
     """3x3/2 max-pool with padding 1 (the ResNet stem pool)."""
 
@@ -264,7 +355,8 @@ def refresh_all_shadows(model: nn.Module):
     multi-tensor kernels."""
     dsts, srcs = [], []
     for m in model.modules():
-        if isinstance(m, (ConvBNAct, Linear, DepthwiseConvBNAct)) \
+        if isinstance(m, (ConvBNAct, Linear, DepthwiseConvBNAct,
+                          GroupedConvBNAct)) \
                 and not getattr(m, "_managed", False):
             if (m.weight_bf16.shape != m.weight.shape
                     or m.weight_bf16.device != m.weight.device):

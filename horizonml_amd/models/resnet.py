@@ -18,7 +18,8 @@ from typing import List, Tuple
 import torch
 import torch.nn as nn
 
-from .layers import ConvBNAct, GlobalAvgPool, Linear, MaxPool2d3x3s2
+from .layers import (ConvBNAct, GlobalAvgPool, GroupedConvBNAct, Linear,
+                     MaxPool2d3x3s2)
 
 
 class BasicBlock(nn.Module):
@@ -50,12 +51,21 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     expansion = 4
 
-    def __init__(self, in_ch: int, ch: int, stride: int = 1):
+    def __init__(self, in_ch: int, ch: int, stride: int = 1,
+                 groups: int = 1, base_width: int = 64):
         super().__init__()
         out_ch = ch * self.expansion
-        self.conv1 = ConvBNAct(in_ch, ch, 1, stride=1, act=True)
-        self.conv2 = ConvBNAct(ch, ch, 3, stride=stride, act=True)
-        self.conv3 = ConvBNAct(ch, out_ch, 1, stride=1, act=True)
+        # ResNeXt: the 3x3 is a grouped conv of `groups` x `base_width`-scaled
+        # channels; the defaults give width == ch and a dense 3x3 (ResNet)
+        width = int(ch * (base_width / 64.0)) * groups
+        self.conv1 = ConvBNAct(in_ch, width, 1, stride=1, act=True)
+        if groups > 1:
+            # runs per module on the GPU: _fusable() is False for this block
+            self.conv2 = GroupedConvBNAct(width, width, 3, stride=stride,
+                                          groups=groups, act=True)
+        else:
+            self.conv2 = ConvBNAct(width, width, 3, stride=stride, act=True)
+        self.conv3 = ConvBNAct(width, out_ch, 1, stride=1, act=True)
         self.downsample = (ConvBNAct(in_ch, out_ch, 1, stride=stride, act=False)
                            if (stride != 1 or in_ch != out_ch) else None)
 
@@ -108,9 +118,13 @@ class Tail(nn.Module):
 
 class ResNet(nn.Module):
     def __init__(self, block, layers: List[int], num_classes: int = 10,
-                 stem: str = "imagenet", width: int = 64):
+                 stem: str = "imagenet", width: int = 64, groups: int = 1,
+                 width_per_group: int = 64):
         super().__init__()
+        if (groups != 1 or width_per_group != 64) and block is not Bottleneck:
+            raise ValueError("groups / width_per_group need Bottleneck blocks")
         self.block_type = block
+        self.groups, self.base_width = groups, width_per_group
         self.stem = Stem(stem, width)
         self.in_ch = width
         self.layer1 = self._make_layer(block, width, layers[0], 1)
@@ -120,10 +134,13 @@ class ResNet(nn.Module):
         self.tail = Tail(width * 8 * block.expansion, num_classes)
 
     def _make_layer(self, block, ch: int, n: int, stride: int) -> nn.Sequential:
-        blocks = [block(self.in_ch, ch, stride)]
+        # only the ResNeXt variants pass the extra arguments on
+        kw = ({} if self.groups == 1 and self.base_width == 64
+              else dict(groups=self.groups, base_width=self.base_width))
+        blocks = [block(self.in_ch, ch, stride, **kw)]
         self.in_ch = ch * block.expansion
         for _ in range(n - 1):
-            blocks.append(block(self.in_ch, ch, 1))
+            blocks.append(block(self.in_ch, ch, 1, **kw))
         return nn.Sequential(*blocks)
 
     def forward(self, x):
@@ -173,6 +190,13 @@ def resnet50(num_classes: int = 1000, stem: str = "imagenet") -> ResNet:
     return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, stem)
 
 
+def resnext50_32x4d(num_classes: int = 1000, stem: str = "imagenet") -> ResNet:
+    """ResNeXt-50 32x4d: the resnet50 layout with a 32-group 3x3 of 4, 8, 16
+    and 32 channels per group in layers 1 to 4."""
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, stem, groups=32,
+                  width_per_group=4)
+
+
 def build_model(name: str, num_classes: int = 10, stem: str = "imagenet") -> nn.Module:
     name = name.lower()
     if name in ("resnet18", "resnet"):
@@ -181,6 +205,8 @@ def build_model(name: str, num_classes: int = 10, stem: str = "imagenet") -> nn.
         return resnet34(num_classes, stem)
     if name == "resnet50":
         return resnet50(num_classes, stem)
+    if name in ("resnext50", "resnext50_32x4d"):
+        return resnext50_32x4d(num_classes, stem)
     if name in ("mobilenet", "mobilenet_v2"):
         from .mobilenet import mobilenet_v2
         return mobilenet_v2(num_classes)

@@ -865,6 +865,270 @@ std::vector<Tensor> dw_conv_bn_bwd(
   return {dx, dw, sum_dzx, sum_dz, dres};
 }
 
+// ------------------------------------------------------ grouped convolution --
+// 1 < groups < C on the grouped_kernels.hip MFMA kernels.  The kernels serve
+// Cg == Kg in {4, 8, 16, 32} (so C == K), a square 1x1 or 3x3 filter, stride
+// 1 or 2 and C % 16 == 0; everything else is refused here, before any
+// launch.  w is the bf16 [K,R,S,Cg] weight; groups = C / Cg.
+GConvP check_grouped_geometry(int64_t Nb, int64_t C, int64_t H, int64_t W,
+                              int64_t K, int64_t R, int64_t S, int64_t Cg,
+                              int64_t stride, int64_t pad) {
+  TORCH_CHECK(Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32,
+              "grouped conv: channels per group must be 4, 8, 16 or 32, got ",
+              Cg);
+  TORCH_CHECK(C % 16 == 0, "grouped conv: C must be a multiple of 16, got ",
+              C);
+  TORCH_CHECK(C % Cg == 0 && K == C,
+              "grouped conv: needs Kg == Cg (K == C, C a multiple of Cg), got"
+              " C=", C, " K=", K, " Cg=", Cg);
+  TORCH_CHECK(C / Cg > 1, "grouped conv: groups must be > 1 (dense convs go "
+              "through conv_bn_act_fwd)");
+  TORCH_CHECK(R == S && (R == 1 || R == 3),
+              "grouped conv: filter must be 1x1 or 3x3, got ", R, "x", S);
+  TORCH_CHECK(stride == 1 || stride == 2,
+              "grouped conv: stride must be 1 or 2, got ", stride);
+  TORCH_CHECK(pad >= 0, "grouped conv: pad must be >= 0, got ", pad);
+  TORCH_CHECK(Nb >= 1 && H + 2 * pad >= R && W + 2 * pad >= S,
+              "grouped conv: output must be at least 1x1: input ", H, "x", W,
+              ", pad ", pad, ", filter ", R, "x", S);
+  const int64_t Ho = (H + 2 * pad - R) / stride + 1;
+  const int64_t Wo = (W + 2 * pad - S) / stride + 1;
+  TORCH_CHECK(Nb * H * W < (1LL << 31) - 4096 &&
+                  Nb * Ho * Wo < (1LL << 31) - 4096,
+              "grouped conv: N*H*W must stay below 2^31");
+  // the grids are flat: (C/16 slabs) x (row chunks)
+  TORCH_CHECK((Nb * H * W / GCONV_MCHUNK + 1) * (C / 16) < (1LL << 31),
+              "grouped conv: too many blocks for one grid");
+  GConvP p{};
+  p.Nb = (int)Nb;
+  p.H = (int)H;
+  p.W = (int)W;
+  p.C = (int)C;
+  p.Ho = (int)Ho;
+  p.Wo = (int)Wo;
+  p.R = (int)R;
+  p.str = (int)stride;
+  p.pad = (int)pad;
+  p.Cg = (int)Cg;
+  p.cgs = Cg == 4 ? 2 : Cg == 8 ? 3 : Cg == 16 ? 4 : 5;
+  p.M = (int)(Nb * Ho * Wo);
+  p.Mi = (int)(Nb * H * W);
+  return p;
+}
+
+GConvP check_grouped_geometry(int64_t Nb, int64_t C, int64_t H, int64_t W,
+                              const Tensor& w, int64_t stride, int64_t pad) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 &&
+                  w.is_contiguous() && w.dim() == 4,
+              "grouped conv: w must be contiguous bf16 [K,R,S,Cg] on GPU");
+  return check_grouped_geometry(Nb, C, H, W, w.size(0), w.size(1), w.size(2),
+                                w.size(3), stride, pad);
+}
+
+void check_nchw(const Tensor& t, int64_t n, int64_t c, int64_t h, int64_t w,
+                const char* what) {
+  TORCH_CHECK(t.size(0) == n && t.size(1) == c && t.size(2) == h &&
+                  t.size(3) == w,
+              what);
+}
+
+// dw f32 [K,R,S,Cg] (+)= the grouped weight gradient; immediate mode
+void grouped_wgrad_into(const Tensor& x, const Tensor& dz, const Tensor& dw,
+                        const GConvP& p, hipStream_t st) {
+  const int msplit = gconv_wgrad_msplit(p);
+  Tensor ws;
+  float* ws_ptr = nullptr;
+  if (msplit > 1) {
+    ws = at::empty({gconv_wgrad_ws_floats(p, msplit)},
+                   x.options().dtype(torch::kFloat32));
+    ws_ptr = ws.data_ptr<float>();
+  }
+  launch_gconv_wgrad(x.data_ptr(), dz.data_ptr(), dw.data_ptr<float>(),
+                     ws_ptr, p, msplit, st);
+}
+
+// (direct, split) grouped wgrad launches so far in this process.
+std::vector<int64_t> grouped_wgrad_launches() {
+  long d = 0, s = 0;
+  gconv_wgrad_launch_counts(&d, &s);
+  return {(int64_t)d, (int64_t)s};
+}
+
+// Raw kernel: convout bf16 [Nb,K,Ho,Wo].  stats: optional pre-zeroed f32
+// [2K] that receives Σy and Σy² of the unrounded accumulators.
+Tensor grouped_conv_fwd(Tensor x, Tensor w, int64_t stride, int64_t pad,
+                        c10::optional<Tensor> stats) {
+  check_cl(x, "x");
+  const GConvP p = check_grouped_geometry(x.size(0), x.size(1), x.size(2),
+                                          x.size(3), w, stride, pad);
+  if (stats.has_value()) {
+    check_f32(*stats, "stats");
+    TORCH_CHECK(stats->dim() == 1 && stats->size(0) == 2L * p.C,
+                "stats must be f32 [2K]");
+  }
+  Tensor y = empty_cl_bf16(p.Nb, p.C, p.Ho, p.Wo, x);
+  launch_gconv_fwd(x.data_ptr(), w.data_ptr(), y.data_ptr(),
+                   opt_ptr<float>(stats), p, cur_stream());
+  return y;
+}
+
+// Raw kernel: dx bf16 [Nb,C,H,W] from dz [Nb,K,Ho,Wo].
+Tensor grouped_conv_dgrad(Tensor dz, Tensor w, int64_t H, int64_t W,
+                          int64_t stride, int64_t pad) {
+  check_cl(dz, "dz");
+  const GConvP p = check_grouped_geometry(dz.size(0), dz.size(1), H, W, w,
+                                          stride, pad);
+  check_nchw(dz, p.Nb, p.C, p.Ho, p.Wo,
+             "dz shape does not match the grouped output of H, W, stride, pad");
+  Tensor dx = empty_cl_bf16(p.Nb, p.C, p.H, p.W, dz);
+  launch_gconv_dgrad(dz.data_ptr(), w.data_ptr(), dx.data_ptr(), p,
+                     cur_stream());
+  return dx;
+}
+
+// Raw kernel: dw f32 [K,R,S,Cg]; dw_out accumulates (read-add-write).
+Tensor grouped_conv_wgrad(Tensor x, Tensor dz, int64_t R, int64_t S,
+                          int64_t stride, int64_t pad, int64_t groups,
+                          c10::optional<Tensor> dw_out) {
+  check_cl(x, "x");
+  check_cl(dz, "dz");
+  const int64_t C = x.size(1);
+  TORCH_CHECK(groups >= 1 && C % groups == 0 && R >= 1 && S >= 1,
+              "grouped conv: groups must divide C");
+  const GConvP p = check_grouped_geometry(x.size(0), C, x.size(2), x.size(3),
+                                          C, R, S, C / groups, stride, pad);
+  check_nchw(dz, p.Nb, p.C, p.Ho, p.Wo,
+             "dz shape does not match the grouped output of x");
+  Tensor dw;
+  if (dw_out.has_value()) {
+    dw = *dw_out;
+    check_f32(dw, "dw_out");
+    TORCH_CHECK(dw.dim() == 4 && dw.size(0) == C && dw.size(1) == R &&
+                    dw.size(2) == S && dw.size(3) == p.Cg,
+                "dw_out must be f32 [K,R,S,Cg]");
+  } else {
+    dw = at::zeros({C, R, S, (int64_t)p.Cg},
+                   x.options().dtype(torch::kFloat32));
+  }
+  grouped_wgrad_into(x, dz, dw, p, cur_stream());
+  return dw;
+}
+
+// Fused forward, the structure of dw_conv_bn_fwd: conv (+ stats epilogue),
+// the fixed-order stats pass in deterministic mode, BN apply with residual,
+// activation, running statistics and eval mode.
+std::vector<Tensor> grouped_conv_bn_fwd(
+    Tensor x, Tensor w, Tensor gamma, Tensor beta, Tensor running_mean,
+    Tensor running_var, int64_t stride, int64_t pad, double momentum,
+    double eps, bool training, int64_t act, c10::optional<Tensor> residual) {
+  check_cl(x, "x");
+  const GConvP p = check_grouped_geometry(x.size(0), x.size(1), x.size(2),
+                                          x.size(3), w, stride, pad);
+  const int C = p.C;
+  for (const Tensor* t : {&gamma, &beta, &running_mean, &running_var}) {
+    check_f32(*t, "BN parameters and running statistics");
+    TORCH_CHECK(t->dim() == 1 && t->size(0) == C,
+                "BN parameters and running statistics must be f32 [K]");
+  }
+  const long M = p.M;
+  auto fopt = x.options().dtype(torch::kFloat32);
+  Tensor convout = empty_cl_bf16(p.Nb, C, p.Ho, p.Wo, x);
+  Tensor y = empty_cl_bf16(p.Nb, C, p.Ho, p.Wo, x);
+  Tensor stats, smean, sinvstd;
+  float* stats_ptr = nullptr;
+  if (training) {
+    stats = at::zeros({2L * C}, fopt);
+    smean = at::empty({C}, fopt);
+    sinvstd = at::empty({C}, fopt);
+    stats_ptr = stats.data_ptr<float>();
+  } else {
+    smean = at::empty({0}, fopt);
+    sinvstd = at::empty({0}, fopt);
+  }
+  const void* res_ptr = nullptr;
+  if (residual.has_value()) {
+    check_cl(*residual, "residual");
+    check_nchw(*residual, p.Nb, C, p.Ho, p.Wo,
+               "residual shape does not match the grouped output");
+    res_ptr = residual->data_ptr();
+  }
+  auto st = cur_stream();
+  launch_gconv_fwd(x.data_ptr(), w.data_ptr(), convout.data_ptr(),
+                   g_deterministic ? nullptr : stats_ptr, p, st);
+  if (g_deterministic && training)
+    launch_stats_bf16_det(convout.data_ptr(), stats_ptr, M, C, st);
+  launch_bn_apply(convout.data_ptr(), res_ptr, y.data_ptr(), stats_ptr,
+                  gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                  running_mean.data_ptr<float>(),
+                  running_var.data_ptr<float>(),
+                  training ? smean.data_ptr<float>() : nullptr,
+                  training ? sinvstd.data_ptr<float>() : nullptr, M, C,
+                  (float)momentum, (float)eps, training ? 1 : 0, (int)act,
+                  st);
+  return {y, convout, smean, sinvstd};
+}
+
+// Fused backward, the structure of dw_conv_bn_bwd: BN-backward reduce and
+// apply, then the grouped wgrad and dgrad.
+std::vector<Tensor> grouped_conv_bn_bwd(
+    Tensor dy, Tensor y, Tensor x, Tensor w, Tensor convout, Tensor gamma,
+    Tensor beta, Tensor save_mean, Tensor save_invstd, int64_t stride,
+    int64_t pad, int64_t act, bool need_dx, bool has_res) {
+  check_cl(dy, "dy");
+  check_cl(y, "y");
+  check_cl(x, "x");
+  check_cl(convout, "convout");
+  const GConvP p = check_grouped_geometry(x.size(0), x.size(1), x.size(2),
+                                          x.size(3), w, stride, pad);
+  const int C = p.C;
+  check_nchw(dy, p.Nb, C, p.Ho, p.Wo,
+             "dy shape does not match the grouped output of x");
+  check_nchw(y, p.Nb, C, p.Ho, p.Wo,
+             "y shape does not match the grouped output of x");
+  check_nchw(convout, p.Nb, C, p.Ho, p.Wo,
+             "convout shape does not match the grouped output of x");
+  for (const Tensor* t : {&gamma, &beta, &save_mean, &save_invstd}) {
+    check_f32(*t, "BN parameters and saved statistics");
+    TORCH_CHECK(t->dim() == 1 && t->size(0) == C,
+                "BN parameters and saved statistics must be f32 [K]");
+  }
+  const long M = p.M;
+  auto fopt = x.options().dtype(torch::kFloat32);
+  auto st = cur_stream();
+  int mask_mode = act == 1 ? (has_res ? 1 : 2)
+                 : act == 2 ? (has_res ? 3 : 4) : 0;
+  Tensor sum_dz = at::zeros({C}, fopt);
+  Tensor sum_dzx = at::zeros({C}, fopt);
+  launch_bnact_bwd_reduce(dy.data_ptr(), y.data_ptr(), convout.data_ptr(),
+                          save_mean.data_ptr<float>(),
+                          save_invstd.data_ptr<float>(),
+                          gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                          sum_dz.data_ptr<float>(), sum_dzx.data_ptr<float>(),
+                          M, C, mask_mode, st);
+  Tensor dconv = empty_cl_bf16(p.Nb, C, p.Ho, p.Wo, x);
+  Tensor dres;
+  void* dres_ptr = nullptr;
+  if (has_res) {
+    dres = empty_cl_bf16(p.Nb, C, p.Ho, p.Wo, x);
+    dres_ptr = dres.data_ptr();
+  }
+  launch_bn_bwd_apply(dy.data_ptr(), y.data_ptr(), convout.data_ptr(),
+                      save_mean.data_ptr<float>(),
+                      save_invstd.data_ptr<float>(), gamma.data_ptr<float>(),
+                      beta.data_ptr<float>(), sum_dz.data_ptr<float>(),
+                      sum_dzx.data_ptr<float>(), dconv.data_ptr(), dres_ptr,
+                      M, C, mask_mode, st);
+  Tensor dw = at::zeros({(int64_t)C, (int64_t)p.R, (int64_t)p.R,
+                         (int64_t)p.Cg}, fopt);
+  grouped_wgrad_into(x, dconv, dw, p, st);
+  Tensor dx;
+  if (need_dx) {
+    dx = empty_cl_bf16(p.Nb, C, p.H, p.W, x);
+    launch_gconv_dgrad(dconv.data_ptr(), w.data_ptr(), dx.data_ptr(), p, st);
+  }
+  return {dx, dw, sum_dzx, sum_dz, dres};
+}
+
 // ----------------------------------------------------------------- pools --
 std::vector<Tensor> maxpool_fwd(Tensor x) {
   check_cl(x, "x");
@@ -1575,6 +1839,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv_bn_act_bwd", &conv_bn_act_bwd);
   m.def("dw_conv_bn_fwd", &dw_conv_bn_fwd);
   m.def("dw_conv_bn_bwd", &dw_conv_bn_bwd);
+  m.def("grouped_conv_fwd", &grouped_conv_fwd, py::arg("x"), py::arg("w"),
+        py::arg("stride"), py::arg("pad"), py::arg("stats") = py::none());
+  m.def("grouped_conv_dgrad", &grouped_conv_dgrad);
+  m.def("grouped_conv_wgrad", &grouped_conv_wgrad, py::arg("x"),
+        py::arg("dz"), py::arg("R"), py::arg("S"), py::arg("stride"),
+        py::arg("pad"), py::arg("groups"), py::arg("dw_out") = py::none());
+  m.def("grouped_conv_bn_fwd", &grouped_conv_bn_fwd);
+  m.def("grouped_conv_bn_bwd", &grouped_conv_bn_bwd);
+  m.def("grouped_wgrad_launches", &grouped_wgrad_launches);
   m.def("maxpool_fwd", &maxpool_fwd);
   m.def("maxpool_bwd", &maxpool_bwd);
   m.def("avgpool_fwd", &avgpool_fwd);

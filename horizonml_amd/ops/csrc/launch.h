@@ -93,6 +93,22 @@ static_assert(std::is_trivially_copyable_v<WgradBatchArgs> &&
                   std::is_trivially_copyable_v<WredBatchArgs>,
               "batched wgrad task tables are copied into the kernarg segment");
 
+// Grouped convolution (grouped_kernels.hip), 1 < groups < C.  Cg == Kg, so
+// C == K; the weight is [K][R][R][Cg].
+struct GConvP {
+  int Nb, H, W, C;   // batch, input spatial, channels (in == out)
+  int Ho, Wo, R;     // output spatial, square filter
+  int str, pad;
+  int Cg, cgs;       // channels per group (4, 8, 16 or 32) and its log2
+  int M, Mi;         // Nb*Ho*Wo (forward / wgrad rows), Nb*H*W (dgrad rows)
+};
+
+// Rows of one forward / dgrad block, and of one wgrad split by default
+// (HZ_GCONV_WGRAD_MCHUNK); the wgrad split count is capped.
+constexpr int GCONV_MCHUNK = 256;
+constexpr int GCONV_WGRAD_MCHUNK = 1024;
+constexpr int GCONV_WGRAD_MAXSPLIT = 64;
+
 // Widest row of the wave-per-row CE: four f32 rows fill the 64 KB of LDS a
 // kernel gets without opting in to more.
 constexpr int CE_WIDE_MAX_NC = 4096;
@@ -335,6 +351,23 @@ void launch_head_bwd(const float* dy, const void* x, const void* w, void* dx,
 void launch_ce_wide(const float* logits, const long* target, float* loss,
                     float* dlogits, int B, int NC, float eps, int ls,
                     hipStream_t st);
+
+// grouped_kernels.hip: x, dz, y, dx bf16 NHWC, w bf16 [K][R][R][Cg].  The
+// caller (bind.cpp, check_grouped_geometry) guarantees the domain: Cg in
+// {4, 8, 16, 32}, R in {1, 3}, str in {1, 2}, C % 16 == 0, M and Mi < 2^31.
+// stats: pre-zeroed f32 [2C] (Σy, Σy²) or nullptr.
+void launch_gconv_fwd(const void* x, const void* w, void* y, float* stats,
+                      GConvP p, hipStream_t st);
+void launch_gconv_dgrad(const void* dz, const void* w, void* dx, GConvP p,
+                        hipStream_t st);
+// m-splits of the wgrad at this geometry; > 1 needs a workspace of
+// gconv_wgrad_ws_floats(p, msplit) floats
+int gconv_wgrad_msplit(GConvP p);
+long gconv_wgrad_ws_floats(GConvP p, int msplit);
+// dw f32 [K][R][R][Cg] is read-add-written; no atomics
+void launch_gconv_wgrad(const void* x, const void* dz, float* dw, float* ws,
+                        GConvP p, int msplit, hipStream_t st);
+void gconv_wgrad_launch_counts(long* direct, long* split);
 
 // elem_kernels.hip: optimizers.  step_t is the device step counter; the
 // Adam launchers (and SGD with a table) increment it before the update.

@@ -143,17 +143,20 @@ def grad_units(model: torch.nn.Module):
     Units follow ``model.parameters()`` order, so each unit's params are a
     contiguous run of the flat buffer.
     """
-    from ..models.layers import ConvBNAct, DepthwiseConvBNAct, Linear
+    from ..models.layers import (ConvBNAct, DepthwiseConvBNAct,
+                                 GroupedConvBNAct, Linear)
     from ..models.resnet import BasicBlock, Bottleneck
 
     units = []
 
     def walk(m):
-        if isinstance(m, (BasicBlock, Bottleneck)):
+        if isinstance(m, (BasicBlock, Bottleneck)) and m._fusable():
             # fused res_block: one autograd node; callback lands on conv1
             units.append((m.conv1, list(m.parameters())))
             return
-        if isinstance(m, (ConvBNAct, DepthwiseConvBNAct, Linear)):
+        # (a grouped bottleneck runs per module: its convs are units)
+        if isinstance(m, (ConvBNAct, DepthwiseConvBNAct, GroupedConvBNAct,
+                          Linear)):
             units.append((m, list(m.parameters())))
             return
         for c in m.children():

@@ -20,14 +20,17 @@ CSRC = os.path.join(ROOT, "horizonml_amd", "ops", "csrc")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
-HIP_SOURCES = ["conv_kernels.hip", "elem_kernels.hip", "head_kernels.hip"]
+HIP_SOURCES = ["conv_kernels.hip", "elem_kernels.hip", "head_kernels.hip",
+               "grouped_kernels.hip"]
 HIPCC_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
                "-ffast-math"]
-# per-file additions: head_kernels.hip is compiled without packed-f32 VALU
-# ops as a whole (elem_kernels.hip marks single kernels, HZ_NO_PK_F32)
+# per-file additions: head_kernels.hip and grouped_kernels.hip are compiled
+# without packed-f32 VALU ops as a whole (elem_kernels.hip marks single
+# kernels, HZ_NO_PK_F32)
+NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIPCC_FILE_FLAGS = {
-    "head_kernels.hip": ["-Xclang", "-target-feature", "-Xclang",
-                         "-packed-fp32-ops"],
+    "head_kernels.hip": NO_PK_F32,
+    "grouped_kernels.hip": NO_PK_F32,
 }
 
 
