@@ -239,6 +239,48 @@ def linear(x, mod):
     return LinearFn.apply(x, mod.weight, mod.bias, mod)
 
 
+class SqueezeExciteFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, w1, b1, w2, b2, residual, mod):
+        u = _cl(u)
+        if residual is not None:
+            residual = _cl(residual)
+        w1_bf16, w2_bf16 = mod.fc1._shadow(), mod.fc2._shadow()
+        y, s, h, g = _C().se_fwd(u, w1_bf16, b1, w2_bf16, b2, residual,
+                                 mod.act)
+        ctx.save_for_backward(u, y, w1_bf16, w2_bf16, s, h, g)
+        ctx.mod = mod
+        ctx.has_res = residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        u, y, w1_bf16, w2_bf16, s, h, g = ctx.saved_tensors
+        mod = ctx.mod
+        dy = _cl(dy.to(torch.bfloat16) if dy.dtype != torch.bfloat16 else dy)
+        # direct-grad mode, as LinearFn: add straight into the flat .grad views
+        direct = all(getattr(fc, "_managed", False)
+                     and fc.weight.grad is not None
+                     and fc.bias.grad is not None
+                     for fc in (mod.fc1, mod.fc2))
+        outs = ((mod.fc1.weight.grad, mod.fc1.bias.grad,
+                 mod.fc2.weight.grad, mod.fc2.bias.grad) if direct
+                else (None, None, None, None))
+        du, dres, dw1, db1, dw2, db2 = _C().se_bwd(
+            dy, y, u, w1_bf16, w2_bf16, s, h, g, mod.act, ctx.has_res, *outs)
+        _bwd_done(mod.fc2)
+        _bwd_done(mod.fc1)
+        dres = dres if ctx.has_res else None
+        if direct:
+            return (du, None, None, None, None, dres, None)
+        return (du, dw1, db1, dw2, db2, dres, None)
+
+
+def squeeze_excite(u, mod, residual=None):
+    return SqueezeExciteFn.apply(u, mod.fc1.weight, mod.fc1.bias,
+                                 mod.fc2.weight, mod.fc2.bias, residual, mod)
+
+
 class CrossEntropyFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, logits, target, label_smoothing=0.0):

@@ -347,6 +347,44 @@ class Linear(nn.Module):
         return F.linear(x, self.weight, self.bias)
 
 
+class SqueezeExcite(nn.Module):
+    """Squeeze-and-Excitation gate (SENet): ``y = act(u * g + residual)`` with
+    ``g = sigmoid(fc2(relu(fc1(mean_hw(u)))))``, one gate per (image,
+    channel).  On the GPU the whole op is the seven kernels of
+    ``se_kernels.hip`` (three forward, four backward).
+
+    The two layers are ``Linear`` children on purpose: the flat engine wires
+    their bf16 shadows and flat gradient views, ``refresh_all_shadows``
+    refreshes them, their biases land in the no-decay group and
+    ``grad_units`` lists them as units, all without knowing about SE."""
+
+    def __init__(self, ch: int, reduction: int = 16, act=True):
+        super().__init__()
+        if reduction < 1 or ch % reduction:
+            raise ValueError(f"reduction={reduction} must divide ch={ch}")
+        self.ch, self.reduction = ch, reduction
+        self.act = 1 if act else 0
+        self.fc1 = Linear(ch, ch // reduction)
+        self.fc2 = Linear(ch // reduction, ch)
+
+    def extra_repr(self):
+        return f"{self.ch}, reduction={self.reduction}, act={self.act}"
+
+    def forward(self, u: torch.Tensor,
+                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if _use_hip(u):
+            from . import _functional_gpu as FG
+            return FG.squeeze_excite(u, self, residual)
+        # CPU reference path
+        s = u.mean((2, 3))
+        h = F.relu(F.linear(s, self.fc1.weight, self.fc1.bias))
+        g = torch.sigmoid(F.linear(h, self.fc2.weight, self.fc2.bias))
+        y = u * g[:, :, None, None]
+        if residual is not None:
+            y = y + residual
+        return F.relu(y) if self.act else y
+
+
 def refresh_all_shadows(model: nn.Module):
     """Refresh every bf16 weight shadow in `model`.
 

@@ -19,7 +19,7 @@ import torch
 import torch.nn as nn
 
 from .layers import (ConvBNAct, GlobalAvgPool, GroupedConvBNAct, Linear,
-                     MaxPool2d3x3s2)
+                     MaxPool2d3x3s2, SqueezeExcite)
 
 
 class BasicBlock(nn.Module):
@@ -52,7 +52,8 @@ class Bottleneck(nn.Module):
     expansion = 4
 
     def __init__(self, in_ch: int, ch: int, stride: int = 1,
-                 groups: int = 1, base_width: int = 64):
+                 groups: int = 1, base_width: int = 64,
+                 se_reduction: int = 0):
         super().__init__()
         out_ch = ch * self.expansion
         # ResNeXt: the 3x3 is a grouped conv of `groups` x `base_width`-scaled
@@ -65,12 +66,21 @@ class Bottleneck(nn.Module):
                                           groups=groups, act=True)
         else:
             self.conv2 = ConvBNAct(width, width, 3, stride=stride, act=True)
-        self.conv3 = ConvBNAct(width, out_ch, 1, stride=1, act=True)
+        # SE block: conv3 ends at its BN; the gate, the block residual and the
+        # final ReLU are the SE op's.  Runs per module on the GPU.
+        self.conv3 = ConvBNAct(width, out_ch, 1, stride=1,
+                               act=se_reduction <= 0)
         self.downsample = (ConvBNAct(in_ch, out_ch, 1, stride=stride, act=False)
                            if (stride != 1 or in_ch != out_ch) else None)
+        # registered last and only when asked for: the default block keeps
+        # its modules, parameter order and state_dict keys
+        if se_reduction > 0:
+            self.se = SqueezeExcite(out_ch, se_reduction)
 
     def _fusable(self) -> bool:
-        return (type(self.conv1) is ConvBNAct and type(self.conv2) is ConvBNAct
+        return (getattr(self, "se", None) is None
+                and type(self.conv1) is ConvBNAct
+                and type(self.conv2) is ConvBNAct
                 and type(self.conv3) is ConvBNAct
                 and (self.downsample is None
                      or type(self.downsample) is ConvBNAct))
@@ -83,6 +93,8 @@ class Bottleneck(nn.Module):
         identity = self.downsample(x) if self.downsample is not None else x
         out = self.conv1(x)
         out = self.conv2(out)
+        if getattr(self, "se", None) is not None:
+            return self.se(self.conv3(out), identity)
         return self.conv3(out, residual=identity)
 
 
@@ -119,12 +131,15 @@ class Tail(nn.Module):
 class ResNet(nn.Module):
     def __init__(self, block, layers: List[int], num_classes: int = 10,
                  stem: str = "imagenet", width: int = 64, groups: int = 1,
-                 width_per_group: int = 64):
+                 width_per_group: int = 64, se_reduction: int = 0):
         super().__init__()
-        if (groups != 1 or width_per_group != 64) and block is not Bottleneck:
-            raise ValueError("groups / width_per_group need Bottleneck blocks")
+        if ((groups != 1 or width_per_group != 64 or se_reduction)
+                and block is not Bottleneck):
+            raise ValueError("groups / width_per_group / se_reduction need "
+                             "Bottleneck blocks")
         self.block_type = block
         self.groups, self.base_width = groups, width_per_group
+        self.se_reduction = se_reduction
         self.stem = Stem(stem, width)
         self.in_ch = width
         self.layer1 = self._make_layer(block, width, layers[0], 1)
@@ -134,9 +149,11 @@ class ResNet(nn.Module):
         self.tail = Tail(width * 8 * block.expansion, num_classes)
 
     def _make_layer(self, block, ch: int, n: int, stride: int) -> nn.Sequential:
-        # only the ResNeXt variants pass the extra arguments on
+        # only the ResNeXt and SE variants pass the extra arguments on
         kw = ({} if self.groups == 1 and self.base_width == 64
               else dict(groups=self.groups, base_width=self.base_width))
+        if self.se_reduction:
+            kw["se_reduction"] = self.se_reduction
         blocks = [block(self.in_ch, ch, stride, **kw)]
         self.in_ch = ch * block.expansion
         for _ in range(n - 1):
@@ -197,6 +214,19 @@ def resnext50_32x4d(num_classes: int = 1000, stem: str = "imagenet") -> ResNet:
                   width_per_group=4)
 
 
+def se_resnet50(num_classes: int = 1000, stem: str = "imagenet") -> ResNet:
+    """SE-ResNet-50 (SENet): resnet50 with a reduction-16 SE gate per block."""
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, stem,
+                  se_reduction=16)
+
+
+def se_resnext50_32x4d(num_classes: int = 1000,
+                       stem: str = "imagenet") -> ResNet:
+    """SE-ResNeXt-50 32x4d: resnext50_32x4d with the same gate."""
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, stem, groups=32,
+                  width_per_group=4, se_reduction=16)
+
+
 def build_model(name: str, num_classes: int = 10, stem: str = "imagenet") -> nn.Module:
     name = name.lower()
     if name in ("resnet18", "resnet"):
@@ -207,6 +237,10 @@ def build_model(name: str, num_classes: int = 10, stem: str = "imagenet") -> nn.
         return resnet50(num_classes, stem)
     if name in ("resnext50", "resnext50_32x4d"):
         return resnext50_32x4d(num_classes, stem)
+    if name == "se_resnet50":
+        return se_resnet50(num_classes, stem)
+    if name in ("se_resnext50", "se_resnext50_32x4d"):
+        return se_resnext50_32x4d(num_classes, stem)
     if name in ("mobilenet", "mobilenet_v2"):
         from .mobilenet import mobilenet_v2
         return mobilenet_v2(num_classes)

@@ -1246,6 +1246,147 @@ std::vector<Tensor> linear_bwd(Tensor dy, Tensor x, Tensor w, bool need_dx,
   return {dx, dw, db};
 }
 
+// --------------------------------------------------- squeeze-and-excitation --
+// se_kernels.hip.  u [N,C,H,W] bf16 channels_last; w1 [Cr,C], w2 [C,Cr] bf16
+// shadows; b1 [Cr], b2 [C] f32.  Shapes outside the kernels' range are
+// refused here, not run on something slower.
+struct SeShape {
+  int N, C, HW, Cr;
+};
+
+// the streaming kernels and the MLP's f32 reads take 16-byte vectors
+void check_se_al16(const Tensor& t, const char* name) {
+  TORCH_CHECK((size_t)t.data_ptr() % 16 == 0, "se: ", name,
+              " must be 16-byte aligned");
+}
+
+SeShape check_se(const Tensor& u, const Tensor& w1, const Tensor& w2,
+                 const char* op) {
+  check_cl(u, "u");
+  TORCH_CHECK(w1.is_cuda() && w1.is_contiguous() && w1.dim() == 2 &&
+                  w1.scalar_type() == torch::kBFloat16 && w2.is_cuda() &&
+                  w2.is_contiguous() && w2.dim() == 2 &&
+                  w2.scalar_type() == torch::kBFloat16,
+              op, ": w1 and w2 must be contiguous 2-D bf16 on GPU");
+  const int64_t N = u.size(0), C = u.size(1), HW = u.size(2) * u.size(3);
+  const int64_t Cr = w1.size(0);
+  TORCH_CHECK(w1.size(1) == C && w2.size(0) == C && w2.size(1) == Cr, op,
+              ": w1 must be [Cr, C] and w2 [C, Cr] with C = ", C, ", got [",
+              w1.size(0), ", ", w1.size(1), "] and [", w2.size(0), ", ",
+              w2.size(1), "]");
+  TORCH_CHECK(C % 8 == 0 && C <= 2048 && Cr >= 4 && Cr <= 128 && Cr % 4 == 0,
+              op, ": C = ", C, ", Cr = ", Cr,
+              " is outside the kernels' range (C a multiple of 8 up to 2048, "
+              "Cr a multiple of 4 from 4 to 128)");
+  // weight rows are read as 8-byte halves (the flat engine's shadow slices
+  // are unpadded), activations as 16-byte vectors
+  TORCH_CHECK((size_t)w1.data_ptr() % 8 == 0 && (size_t)w2.data_ptr() % 8 == 0,
+              op, ": w1 and w2 must be 8-byte aligned");
+  check_se_al16(u, "u");
+  TORCH_CHECK(N >= 1 && HW >= 1 && N <= 65535 && HW < (1 << 30), op,
+              ": u shape [", N, ", ", C, ", ", u.size(2), ", ", u.size(3),
+              "] is outside the kernels' range");
+  return {(int)N, (int)C, (int)HW, (int)Cr};
+}
+
+void check_se_vec(const Tensor& t, int64_t rows, int64_t cols,
+                  const char* name) {
+  check_f32(t, name);
+  TORCH_CHECK(t.numel() == rows * cols && t.size(0) == rows, "se: ", name,
+              " must have shape [", rows, ", ", cols, "]");
+}
+
+std::vector<Tensor> se_fwd(Tensor u, Tensor w1, Tensor b1, Tensor w2,
+                           Tensor b2, c10::optional<Tensor> residual,
+                           int64_t act) {
+  const SeShape p = check_se(u, w1, w2, "se_fwd");
+  check_se_vec(b1, p.Cr, 1, "b1");
+  check_se_vec(b2, p.C, 1, "b2");
+  TORCH_CHECK(act == 0 || act == 1, "se_fwd: act must be 0 (none) or 1 (ReLU)");
+  if (residual.has_value()) {
+    check_cl(*residual, "residual");
+    TORCH_CHECK(residual->sizes() == u.sizes(),
+                "se_fwd: residual shape differs from u");
+    check_se_al16(*residual, "residual");
+  }
+  auto fopt = u.options().dtype(torch::kFloat32);
+  const int splits = se_splits(p.N, p.HW);
+  Tensor part = at::empty({p.N, splits, p.C}, fopt);
+  Tensor s = at::empty({p.N, p.C}, fopt), h = at::empty({p.N, p.Cr}, fopt),
+         g = at::empty({p.N, p.C}, fopt);
+  Tensor y = empty_cl_bf16(p.N, p.C, u.size(2), u.size(3), u);
+  launch_se_fwd(u.data_ptr(), opt_ptr(residual), y.data_ptr(), w1.data_ptr(),
+                b1.data_ptr<float>(), w2.data_ptr(), b2.data_ptr<float>(),
+                part.data_ptr<float>(), s.data_ptr<float>(),
+                h.data_ptr<float>(), g.data_ptr<float>(), p.N, p.HW, p.C,
+                p.Cr, splits, (int)act, cur_stream());
+  return {y, s, h, g};
+}
+
+std::vector<Tensor> se_bwd(Tensor dy, Tensor y, Tensor u, Tensor w1, Tensor w2,
+                           Tensor s, Tensor h, Tensor g, int64_t act,
+                           bool has_res, c10::optional<Tensor> dw1_out,
+                           c10::optional<Tensor> db1_out,
+                           c10::optional<Tensor> dw2_out,
+                           c10::optional<Tensor> db2_out) {
+  const SeShape p = check_se(u, w1, w2, "se_bwd");
+  check_cl(dy, "dy");
+  check_cl(y, "y");
+  TORCH_CHECK(dy.sizes() == u.sizes() && y.sizes() == u.sizes(),
+              "se_bwd: dy and y must have u's shape");
+  TORCH_CHECK(act == 0 || act == 1, "se_bwd: act must be 0 (none) or 1 (ReLU)");
+  check_se_vec(s, p.N, p.C, "s");
+  check_se_vec(h, p.N, p.Cr, "h");
+  check_se_vec(g, p.N, p.C, "g");
+  check_se_al16(dy, "dy");
+  check_se_al16(y, "y");
+  check_se_al16(s, "s");
+  check_se_al16(h, "h");
+  check_se_al16(g, "g");
+  const bool direct = dw1_out.has_value();
+  TORCH_CHECK(direct == db1_out.has_value() && direct == dw2_out.has_value() &&
+                  direct == db2_out.has_value(),
+              "se_bwd: the four gradient destinations are passed together");
+  auto fopt = u.options().dtype(torch::kFloat32);
+  Tensor dw1, db1, dw2, db2;
+  if (direct) {
+    dw1 = *dw1_out, db1 = *db1_out, dw2 = *dw2_out, db2 = *db2_out;
+    check_se_vec(dw1, p.Cr, p.C, "dw1_out");
+    check_se_vec(db1, p.Cr, 1, "db1_out");
+    check_se_vec(dw2, p.C, p.Cr, "dw2_out");
+    check_se_vec(db2, p.C, 1, "db2_out");
+  } else {
+    dw1 = at::empty({p.Cr, p.C}, fopt), db1 = at::empty({p.Cr}, fopt);
+    dw2 = at::empty({p.C, p.Cr}, fopt), db2 = at::empty({p.C}, fopt);
+  }
+  const int splits = se_splits(p.N, p.HW);
+  Tensor part = at::empty({p.N, splits, p.C}, fopt);
+  Tensor dh = at::empty({p.N, p.Cr}, fopt), ds = at::empty({p.N, p.C}, fopt);
+  Tensor du = empty_cl_bf16(p.N, p.C, u.size(2), u.size(3), u), dres;
+  if (has_res) dres = empty_cl_bf16(p.N, p.C, u.size(2), u.size(3), u);
+  launch_se_bwd(dy.data_ptr(), y.data_ptr(), u.data_ptr(), w1.data_ptr(),
+                w2.data_ptr(), s.data_ptr<float>(), h.data_ptr<float>(),
+                g.data_ptr<float>(), part.data_ptr<float>(),
+                dh.data_ptr<float>(), ds.data_ptr<float>(), du.data_ptr(),
+                has_res ? dres.data_ptr() : nullptr, dw1.data_ptr<float>(),
+                db1.data_ptr<float>(), dw2.data_ptr<float>(),
+                db2.data_ptr<float>(), p.N, p.HW, p.C, p.Cr, splits, (int)act,
+                direct ? 1 : 0, cur_stream());
+  return {du, dres, dw1, db1, dw2, db2};
+}
+
+// (forward, backward) SE kernel launches so far in this process.
+std::vector<int64_t> se_launches() {
+  long f = 0, b = 0;
+  se_launch_counts(&f, &b);
+  return {(int64_t)f, (int64_t)b};
+}
+
+// H·W splits the squeeze and the backward reduce take at this shape.
+int64_t se_split_count(int64_t N, int64_t HW) {
+  return se_splits((int)N, (int)HW);
+}
+
 std::vector<Tensor> cross_entropy_fwd_bwd(Tensor logits, Tensor target) {
   check_f32(logits, "logits");
   TORCH_CHECK(target.scalar_type() == torch::kLong && target.is_contiguous());
@@ -1854,6 +1995,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("avgpool_bwd", &avgpool_bwd);
   m.def("linear_fwd", &linear_fwd);
   m.def("linear_bwd", &linear_bwd);
+  m.def("se_fwd", &se_fwd);
+  m.def("se_bwd", &se_bwd);
+  m.def("se_launches", &se_launches);
+  m.def("se_split_count", &se_split_count);
   m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.def("gemm_bf16", &gemm_bf16);
   m.def("adam_step", &adam_step);

@@ -369,6 +369,30 @@ void launch_gconv_wgrad(const void* x, const void* dz, float* dw, float* ws,
                         GConvP p, int msplit, hipStream_t st);
 void gconv_wgrad_launch_counts(long* direct, long* split);
 
+// se_kernels.hip: squeeze-and-excitation.  u, res, y, dy, du, dres bf16 NHWC
+// [N][HW][C]; w1 [Cr][C], w2 [C][Cr] bf16; everything else f32.  The caller
+// (bind.cpp, check_se) guarantees the domain: C % 8 == 0, C <= 2048,
+// 4 <= Cr <= 128, Cr % 4 == 0, N <= 65535; w1, w2 8-byte aligned, u, res, dy,
+// y, s, h, g 16-byte aligned (dw1, dw2 of any f32 alignment).
+// H*W splits of the squeeze / backward reduce (HZ_SE_SPLITS overrides the
+// rule); part is a workspace of N * splits * C floats.
+int se_splits(int N, int HW);
+// res may be nullptr; act: 0 none, 1 ReLU.  Writes y, s [N][C], h [N][Cr]
+// (post-ReLU) and g [N][C].  Three launches.
+void launch_se_fwd(const void* u, const void* res, void* y, const void* w1,
+                   const float* b1, const void* w2, const float* b2,
+                   float* part, float* s, float* h, float* g, int N, int HW,
+                   int C, int Cr, int splits, int act, hipStream_t st);
+// dres may be nullptr; dh [N][Cr] and ds [N][C] are workspaces.  accum != 0
+// adds dw1, db1, dw2, db2 onto their destinations.  Four launches.
+void launch_se_bwd(const void* dy, const void* y, const void* u,
+                   const void* w1, const void* w2, const float* s,
+                   const float* h, const float* g, float* part, float* dh,
+                   float* ds, void* du, void* dres, float* dw1, float* db1,
+                   float* dw2, float* db2, int N, int HW, int C, int Cr,
+                   int splits, int act, int accum, hipStream_t st);
+void se_launch_counts(long* fwd, long* bwd);
+
 // elem_kernels.hip: optimizers.  step_t is the device step counter; the
 // Adam launchers (and SGD with a table) increment it before the update.
 void launch_adam_step(float* master, float* grad, float* m, float* v,

@@ -14,12 +14,16 @@ from __future__ import annotations
 
 import torch.nn as nn
 
-from ..models.layers import ConvBNAct
+from ..models.layers import ConvBNAct, SqueezeExcite
 from ..models.resnet import ResNet, resnet18
 from .tensor_parallel import ColumnParallelLinear, ShardedConvBNAct
 
 
 def _shard_convs(module: nn.Module, world_size: int, rank: int, group):
+    if any(isinstance(m, SqueezeExcite) for m in module.modules()):
+        raise ValueError(
+            "tp mode 'full' cannot shard a model with SqueezeExcite blocks: "
+            "the gate needs every channel of an image on one rank")
     for name, child in module.named_children():
         if isinstance(child, ConvBNAct):
             if child.out_ch % world_size != 0:
