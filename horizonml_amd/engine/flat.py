@@ -34,7 +34,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops as _ops
-from ..models.layers import (ConvBNAct, DepthwiseConvBNAct,
+from ..models.layers import (ConvBNAct, ConvGNAct, DepthwiseConvBNAct,
                              GroupedConvBNAct, Linear)
 
 
@@ -243,7 +243,7 @@ class FlatParamManager:
         convs = []
         for m in model.modules():
             if isinstance(m, (ConvBNAct, Linear, DepthwiseConvBNAct,
-                              GroupedConvBNAct)):
+                              GroupedConvBNAct, ConvGNAct)):
                 woff, wn = self.slices[id(m.weight)]
                 m.weight_bf16 = self.shadow[woff:woff + wn].view(
                     m.weight.shape)

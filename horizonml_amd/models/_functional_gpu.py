@@ -167,6 +167,50 @@ def grouped_conv_bn_act(x, mod, residual=None):
                                     mod.bn_bias, residual, mod)
 
 
+class ConvGNActFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, gn_weight, gn_bias, residual, mod):
+        x = _cl(x)
+        w_bf16 = mod._shadow()
+        if residual is not None:
+            residual = _cl(residual)
+        y, convout, mean, rstd = _C().conv_gn_act_fwd(
+            x, w_bf16, gn_weight, gn_bias, mod.groups, mod.stride,
+            mod.padding, mod.eps, mod.act, residual)
+        ctx.save_for_backward(x, y, convout, w_bf16, gn_weight, mean, rstd)
+        ctx.mod = mod
+        ctx.has_res = residual is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, convout, w_bf16, gamma, mean, rstd = ctx.saved_tensors
+        mod = ctx.mod
+        need_dx = ctx.needs_input_grad[0]
+        dy = _cl(dy.to(torch.bfloat16) if dy.dtype != torch.bfloat16 else dy)
+        # direct-grad mode, as ConvBNActFn: add into the flat .grad views
+        direct = (getattr(mod, "_managed", False)
+                  and mod.weight.grad is not None)
+        dw_out = mod.weight.grad if direct else None
+        dg_out = mod.gn_weight.grad if direct else None
+        db_out = mod.gn_bias.grad if direct else None
+        dx, dw, dgamma, dbeta, dres = _C().conv_gn_act_bwd(
+            dy, y, x, w_bf16, convout, gamma, mean, rstd, mod.groups,
+            mod.stride, mod.padding, mod.act, need_dx, ctx.has_res, dw_out,
+            dg_out, db_out)
+        _bwd_done(mod)
+        if direct:
+            return (dx if need_dx else None, None, None, None,
+                    dres if ctx.has_res else None, None)
+        return (dx if need_dx else None, dw, dgamma, dbeta,
+                dres if ctx.has_res else None, None)
+
+
+def conv_gn_act(x, mod, residual=None):
+    return ConvGNActFn.apply(x, mod.weight, mod.gn_weight, mod.gn_bias,
+                             residual, mod)
+
+
 class MaxPoolFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -282,6 +282,86 @@ class GroupedConvBNAct(nn.Module):
         return y
 
 
+class ConvGNAct(nn.Module):
+    """Fused Conv2d + GroupNorm [+ residual add] [+ act]: the dense MFMA conv
+    without a stats epilogue, then the one-launch GroupNorm of
+    ``gn_kernels.hip`` (statistics per sample and group, so a batch split
+    into microbatches computes the same thing).  Weight layout KRSC.
+
+    A class of its own, not a ``ConvBNAct``: the flat engine's stats arena,
+    RSCK metadata and tap-window table and the residual blocks' fused path
+    key on that type.  No buffers: there are no running statistics and no
+    train/eval split.  The GPU kernels serve 2, 4, 8, 16, 32 or 64 channels
+    per group with ``out_ch`` a multiple of 8 up to 2048."""
+
+    def __init__(self, in_ch: int, out_ch: int, kernel_size: int = 3,
+                 stride: int = 1, padding: Optional[int] = None,
+                 groups: int = 32, act=True, eps: float = 1e-5):
+        super().__init__()
+        if padding is None:
+            padding = kernel_size // 2
+        if groups < 1 or out_ch % groups:
+            raise ValueError(f"groups={groups} must divide out_ch={out_ch}")
+        self.in_ch, self.out_ch, self.groups = in_ch, out_ch, groups
+        self.kernel_size, self.stride, self.padding = (kernel_size, stride,
+                                                       padding)
+        self.act = ConvBNAct.ACT[act] if not isinstance(act, int) else act
+        self.eps = eps
+        self.weight = nn.Parameter(
+            torch.empty(out_ch, kernel_size, kernel_size, in_ch))
+        self.gn_weight = nn.Parameter(torch.ones(out_ch))
+        self.gn_bias = nn.Parameter(torch.zeros(out_ch))
+        self.register_buffer("weight_bf16", torch.empty(0), persistent=False)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        fan_out = self.kernel_size * self.kernel_size * self.out_ch
+        with torch.no_grad():
+            self.weight.normal_(0, math.sqrt(2.0 / fan_out))
+
+    def extra_repr(self):
+        return (f"{self.in_ch}, {self.out_ch}, k={self.kernel_size}, "
+                f"s={self.stride}, p={self.padding}, "
+                f"gn_groups={self.groups}, act={self.act}")
+
+    def refresh_shadow(self):
+        if getattr(self, "_managed", False):
+            return
+        with torch.no_grad():
+            if (self.weight_bf16.shape == self.weight.shape
+                    and self.weight_bf16.device == self.weight.device):
+                self.weight_bf16.copy_(self.weight.detach())
+            else:
+                self.weight_bf16 = self.weight.detach() \
+                    .to(torch.bfloat16).contiguous()
+
+    def _shadow(self) -> torch.Tensor:
+        if getattr(self, "_managed", False):
+            return self.weight_bf16
+        if (self.weight_bf16.numel() != self.weight.numel()
+                or self.weight_bf16.device != self.weight.device):
+            self.refresh_shadow()
+        return self.weight_bf16
+
+    def forward(self, x: torch.Tensor,
+                residual: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if _use_hip(x):
+            from . import _functional_gpu as FG
+            return FG.conv_gn_act(x, self, residual)
+        # CPU reference path
+        w = self.weight.permute(0, 3, 1, 2)  # KRSC -> OIHW
+        y = F.conv2d(x, w, None, stride=self.stride, padding=self.padding)
+        y = F.group_norm(y, self.groups, self.gn_weight, self.gn_bias,
+                         self.eps)
+        if residual is not None:
+            y = y + residual
+        if self.act == 1:
+            y = F.relu(y)
+        elif self.act == 2:
+            y = F.hardtanh(y, 0.0, 6.0)
+        return y
+
+
 class MaxPool2d3x3s2(nn.Module):
     """3x3/2 max-pool with padding 1 (the ResNet stem pool)."""
 
@@ -394,7 +474,7 @@ def refresh_all_shadows(model: nn.Module):
     dsts, srcs = [], []
     for m in model.modules():
         if isinstance(m, (ConvBNAct, Linear, DepthwiseConvBNAct,
-                          GroupedConvBNAct)) \
+                          GroupedConvBNAct, ConvGNAct)) \
                 and not getattr(m, "_managed", False):
             if (m.weight_bf16.shape != m.weight.shape
                     or m.weight_bf16.device != m.weight.device):

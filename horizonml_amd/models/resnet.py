@@ -18,20 +18,36 @@ from typing import List, Tuple
 import torch
 import torch.nn as nn
 
-from .layers import (ConvBNAct, GlobalAvgPool, GroupedConvBNAct, Linear,
-                     MaxPool2d3x3s2, SqueezeExcite)
+from .layers import (ConvBNAct, ConvGNAct, GlobalAvgPool, GroupedConvBNAct,
+                     Linear, MaxPool2d3x3s2, SqueezeExcite)
+
+
+def _conv_ctor(norm: str, gn_groups: int):
+    """The dense conv+norm+act module of a block: ``ConvBNAct`` for "bn" (the
+    default: same modules, parameter order and state_dict keys as ever), or
+    ``ConvGNAct`` with ``gn_groups`` groups for "gn"."""
+    if norm == "bn":
+        return ConvBNAct
+    if norm != "gn":
+        raise ValueError(f"unknown norm {norm!r} (bn | gn)")
+
+    def make(in_ch, out_ch, kernel_size, **kw):
+        return ConvGNAct(in_ch, out_ch, kernel_size, groups=gn_groups, **kw)
+    return make
 
 
 class BasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, in_ch: int, ch: int, stride: int = 1):
+    def __init__(self, in_ch: int, ch: int, stride: int = 1,
+                 norm: str = "bn", gn_groups: int = 32):
         super().__init__()
-        self.conv1 = ConvBNAct(in_ch, ch, 3, stride=stride, act=True)
-        # conv2 fuses BN + residual add + final ReLU into one epilogue:
-        # out = relu(bn(conv(x)) + identity)
-        self.conv2 = ConvBNAct(ch, ch, 3, stride=1, act=True)
-        self.downsample = (ConvBNAct(in_ch, ch, 1, stride=stride, act=False)
+        conv = _conv_ctor(norm, gn_groups)
+        self.conv1 = conv(in_ch, ch, 3, stride=stride, act=True)
+        # conv2 fuses norm + residual add + final ReLU into one epilogue:
+        # out = relu(norm(conv(x)) + identity)
+        self.conv2 = conv(ch, ch, 3, stride=1, act=True)
+        self.downsample = (conv(in_ch, ch, 1, stride=stride, act=False)
                            if (stride != 1 or in_ch != ch) else None)
 
     def _fusable(self) -> bool:
@@ -53,24 +69,28 @@ class Bottleneck(nn.Module):
 
     def __init__(self, in_ch: int, ch: int, stride: int = 1,
                  groups: int = 1, base_width: int = 64,
-                 se_reduction: int = 0):
+                 se_reduction: int = 0, norm: str = "bn",
+                 gn_groups: int = 32):
         super().__init__()
+        if norm != "bn" and (groups > 1 or se_reduction > 0):
+            raise ValueError("norm='gn' serves dense convs only: not with "
+                             "groups > 1 or se_reduction")
+        conv = _conv_ctor(norm, gn_groups)
         out_ch = ch * self.expansion
         # ResNeXt: the 3x3 is a grouped conv of `groups` x `base_width`-scaled
         # channels; the defaults give width == ch and a dense 3x3 (ResNet)
         width = int(ch * (base_width / 64.0)) * groups
-        self.conv1 = ConvBNAct(in_ch, width, 1, stride=1, act=True)
+        self.conv1 = conv(in_ch, width, 1, stride=1, act=True)
         if groups > 1:
             # runs per module on the GPU: _fusable() is False for this block
             self.conv2 = GroupedConvBNAct(width, width, 3, stride=stride,
                                           groups=groups, act=True)
         else:
-            self.conv2 = ConvBNAct(width, width, 3, stride=stride, act=True)
+            self.conv2 = conv(width, width, 3, stride=stride, act=True)
         # SE block: conv3 ends at its BN; the gate, the block residual and the
         # final ReLU are the SE op's.  Runs per module on the GPU.
-        self.conv3 = ConvBNAct(width, out_ch, 1, stride=1,
-                               act=se_reduction <= 0)
-        self.downsample = (ConvBNAct(in_ch, out_ch, 1, stride=stride, act=False)
+        self.conv3 = conv(width, out_ch, 1, stride=1, act=se_reduction <= 0)
+        self.downsample = (conv(in_ch, out_ch, 1, stride=stride, act=False)
                            if (stride != 1 or in_ch != out_ch) else None)
         # registered last and only when asked for: the default block keeps
         # its modules, parameter order and state_dict keys
@@ -99,14 +119,16 @@ class Bottleneck(nn.Module):
 
 
 class Stem(nn.Module):
-    def __init__(self, kind: str = "imagenet", out_ch: int = 64):
+    def __init__(self, kind: str = "imagenet", out_ch: int = 64,
+                 norm: str = "bn", gn_groups: int = 32):
         super().__init__()
         self.kind = kind
+        conv = _conv_ctor(norm, gn_groups)
         if kind == "imagenet":
-            self.conv = ConvBNAct(3, out_ch, 7, stride=2, padding=3, act=True)
+            self.conv = conv(3, out_ch, 7, stride=2, padding=3, act=True)
             self.pool = MaxPool2d3x3s2()
         elif kind == "cifar":
-            self.conv = ConvBNAct(3, out_ch, 3, stride=1, padding=1, act=True)
+            self.conv = conv(3, out_ch, 3, stride=1, padding=1, act=True)
             self.pool = nn.Identity()
         else:
             raise ValueError(f"unknown stem kind {kind!r}")
@@ -131,8 +153,14 @@ class Tail(nn.Module):
 class ResNet(nn.Module):
     def __init__(self, block, layers: List[int], num_classes: int = 10,
                  stem: str = "imagenet", width: int = 64, groups: int = 1,
-                 width_per_group: int = 64, se_reduction: int = 0):
+                 width_per_group: int = 64, se_reduction: int = 0,
+                 norm: str = "bn", gn_groups: int = 32):
         super().__init__()
+        if norm not in ("bn", "gn"):
+            raise ValueError(f"unknown norm {norm!r} (bn | gn)")
+        if norm == "gn" and (groups != 1 or se_reduction):
+            raise ValueError("norm='gn' serves dense convs only: not with "
+                             "groups > 1 or se_reduction")
         if ((groups != 1 or width_per_group != 64 or se_reduction)
                 and block is not Bottleneck):
             raise ValueError("groups / width_per_group / se_reduction need "
@@ -140,7 +168,9 @@ class ResNet(nn.Module):
         self.block_type = block
         self.groups, self.base_width = groups, width_per_group
         self.se_reduction = se_reduction
-        self.stem = Stem(stem, width)
+        self.norm, self.gn_groups = norm, gn_groups
+        self.stem = (Stem(stem, width) if norm == "bn"
+                     else Stem(stem, width, norm, gn_groups))
         self.in_ch = width
         self.layer1 = self._make_layer(block, width, layers[0], 1)
         self.layer2 = self._make_layer(block, width * 2, layers[1], 2)
@@ -154,6 +184,8 @@ class ResNet(nn.Module):
               else dict(groups=self.groups, base_width=self.base_width))
         if self.se_reduction:
             kw["se_reduction"] = self.se_reduction
+        if self.norm != "bn":
+            kw.update(norm=self.norm, gn_groups=self.gn_groups)
         blocks = [block(self.in_ch, ch, stride, **kw)]
         self.in_ch = ch * block.expansion
         for _ in range(n - 1):
@@ -227,6 +259,20 @@ def se_resnext50_32x4d(num_classes: int = 1000,
                   width_per_group=4, se_reduction=16)
 
 
+def resnet18_gn(num_classes: int = 10, stem: str = "imagenet",
+                gn_groups: int = 32) -> ResNet:
+    """ResNet-18 with GroupNorm in place of every BatchNorm."""
+    return ResNet(BasicBlock, [2, 2, 2, 2], num_classes, stem, norm="gn",
+                  gn_groups=gn_groups)
+
+
+def resnet50_gn(num_classes: int = 1000, stem: str = "imagenet",
+                gn_groups: int = 32) -> ResNet:
+    """ResNet-50 with GroupNorm in place of every BatchNorm."""
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes, stem, norm="gn",
+                  gn_groups=gn_groups)
+
+
 def build_model(name: str, num_classes: int = 10, stem: str = "imagenet") -> nn.Module:
     name = name.lower()
     if name in ("resnet18", "resnet"):
@@ -241,6 +287,10 @@ def build_model(name: str, num_classes: int = 10, stem: str = "imagenet") -> nn.
         return se_resnet50(num_classes, stem)
     if name in ("se_resnext50", "se_resnext50_32x4d"):
         return se_resnext50_32x4d(num_classes, stem)
+    if name == "resnet18_gn":
+        return resnet18_gn(num_classes, stem)
+    if name == "resnet50_gn":
+        return resnet50_gn(num_classes, stem)
     if name in ("mobilenet", "mobilenet_v2"):
         from .mobilenet import mobilenet_v2
         return mobilenet_v2(num_classes)

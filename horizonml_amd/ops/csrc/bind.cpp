@@ -1387,6 +1387,250 @@ int64_t se_split_count(int64_t N, int64_t HW) {
   return se_splits((int)N, (int)HW);
 }
 
+// -------------------------------------------------------------- GroupNorm --
+// gn_kernels.hip.  Activations [N,C,H,W] bf16 channels_last; gamma, beta [C]
+// f32; mean, rstd [N,G] f32.  Shapes outside the kernels' range are refused
+// here, before any launch.
+struct GnShape {
+  int N, C, H, W, HW, G;
+};
+
+GnShape check_gn(int64_t N, int64_t C, int64_t H, int64_t W, int64_t groups,
+                 const char* op) {
+  TORCH_CHECK(groups >= 1 && C % groups == 0, op, ": groups = ", groups,
+              " does not divide C = ", C);
+  const int64_t Cg = C / groups;
+  TORCH_CHECK(C % 8 == 0 && C <= 2048 &&
+                  (Cg == 2 || Cg == 4 || Cg == 8 || Cg == 16 || Cg == 32 ||
+                   Cg == 64),
+              op, ": C = ", C, " with ", Cg, " channels per group is outside "
+              "the kernels' range (C a multiple of 8 up to 2048, 2, 4, 8, 16, "
+              "32 or 64 channels per group)");
+  TORCH_CHECK(N >= 1 && N <= 65535 && H * W >= 1 && H * W <= (1 << 20), op,
+              ": shape [", N, ", ", C, ", ", H, ", ", W,
+              "] is outside the kernels' range");
+  return {(int)N, (int)C, (int)H, (int)W, (int)(H * W), (int)groups};
+}
+
+void check_gn_param(const Tensor& t, int C, const char* name) {
+  check_f32(t, name);
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == C, "gn: ", name,
+              " must be f32 [C]");
+}
+
+void check_gn_act(const Tensor& t, const GnShape& s, const char* name) {
+  check_cl(t, name);
+  TORCH_CHECK(t.size(0) == s.N && t.size(1) == s.C && t.size(2) == s.H &&
+                  t.size(3) == s.W,
+              "gn: ", name, " must be [N,C,H,W] of the normalised tensor");
+  TORCH_CHECK((size_t)t.data_ptr() % 16 == 0, "gn: ", name,
+              " must be 16-byte aligned");
+}
+
+// The forward behind gn_fwd and conv_gn_act_fwd.  slabs == nullptr: convout
+// holds the bf16 conv output; else it receives the slabs' sum.
+std::vector<Tensor> gn_forward(const Tensor& convout, const float* slabs,
+                               int nsplit, const GnShape& s,
+                               const Tensor& gamma, const Tensor& beta,
+                               double eps, int64_t act,
+                               const c10::optional<Tensor>& residual,
+                               hipStream_t st) {
+  check_gn_param(gamma, s.C, "gamma");
+  check_gn_param(beta, s.C, "beta");
+  TORCH_CHECK(act >= 0 && act <= 2, "gn: act must be 0, 1 (ReLU) or 2 (ReLU6)");
+  if (residual.has_value()) check_gn_act(*residual, s, "residual");
+  auto fopt = convout.options().dtype(torch::kFloat32);
+  Tensor y = empty_cl_bf16(s.N, s.C, s.H, s.W, convout);
+  Tensor mean = at::empty({s.N, s.G}, fopt), rstd = at::empty({s.N, s.G}, fopt);
+  const int Z = gn_splits(s.HW, s.C, s.G, 0);
+  Tensor part;
+  if (Z > 1) part = at::empty({(long)s.N * Z * s.G * 2}, fopt);
+  launch_gn_fwd(convout.data_ptr(), slabs, nsplit, convout.data_ptr(),
+                opt_ptr(residual), y.data_ptr(), gamma.data_ptr<float>(),
+                beta.data_ptr<float>(), mean.data_ptr<float>(),
+                rstd.data_ptr<float>(), Z > 1 ? part.data_ptr<float>() : nullptr,
+                s.N, s.HW, s.C, s.G, (float)eps, (int)act, st);
+  return {y, convout, mean, rstd};
+}
+
+// x: the bf16 conv output [N,C,H,W] (nsplit <= 1), or f32 split-K slabs
+// [nsplit,N,H,W,C].  Returns [y, convout, mean, rstd].
+std::vector<Tensor> gn_fwd(Tensor x, Tensor gamma, Tensor beta, int64_t groups,
+                           double eps, int64_t act,
+                           c10::optional<Tensor> residual, int64_t nsplit) {
+  if (x.scalar_type() == torch::kBFloat16) {
+    check_cl(x, "x");
+    TORCH_CHECK(nsplit <= 1, "gn_fwd: a bf16 source has no slabs");
+    const GnShape s = check_gn(x.size(0), x.size(1), x.size(2), x.size(3),
+                               groups, "gn_fwd");
+    check_gn_act(x, s, "x");
+    return gn_forward(x, nullptr, 0, s, gamma, beta, eps, act, residual,
+                      cur_stream());
+  }
+  check_f32(x, "slabs");
+  TORCH_CHECK(x.dim() == 5 && nsplit >= 1 && x.size(0) == nsplit,
+              "gn_fwd: f32 slabs must be [nsplit,N,H,W,C]");
+  TORCH_CHECK((size_t)x.data_ptr() % 16 == 0,
+              "gn_fwd: slabs must be 16-byte aligned");
+  const GnShape s = check_gn(x.size(1), x.size(4), x.size(2), x.size(3),
+                             groups, "gn_fwd");
+  Tensor convout = empty_cl_bf16(s.N, s.C, s.H, s.W, x);
+  return gn_forward(convout, x.data_ptr<float>(), (int)nsplit, s, gamma, beta,
+                    eps, act, residual, cur_stream());
+}
+
+// The backward behind gn_bwd and conv_gn_act_bwd: [dconv, dres, dgamma,
+// dbeta].  With dgamma_out / dbeta_out the sums are ADDED onto them.
+std::vector<Tensor> gn_backward(const Tensor& dy, const Tensor& y,
+                                const Tensor& convout, const Tensor& gamma,
+                                const Tensor& mean, const Tensor& rstd,
+                                const GnShape& s, int64_t act, bool has_res,
+                                const c10::optional<Tensor>& dgamma_out,
+                                const c10::optional<Tensor>& dbeta_out,
+                                hipStream_t st) {
+  check_gn_act(dy, s, "dy");
+  check_gn_act(y, s, "y");
+  check_gn_act(convout, s, "convout");
+  check_gn_param(gamma, s.C, "gamma");
+  TORCH_CHECK(act >= 0 && act <= 2, "gn: act must be 0, 1 (ReLU) or 2 (ReLU6)");
+  for (const Tensor* t : {&mean, &rstd}) {
+    check_f32(*t, "mean / rstd");
+    TORCH_CHECK(t->dim() == 2 && t->size(0) == s.N && t->size(1) == s.G,
+                "gn: mean and rstd must be f32 [N,G]");
+  }
+  const bool direct = dgamma_out.has_value();
+  TORCH_CHECK(direct == dbeta_out.has_value(),
+              "gn: dgamma_out and dbeta_out are passed together");
+  auto fopt = dy.options().dtype(torch::kFloat32);
+  Tensor dgamma, dbeta;
+  if (direct) {
+    dgamma = *dgamma_out, dbeta = *dbeta_out;
+    check_gn_param(dgamma, s.C, "dgamma_out");
+    check_gn_param(dbeta, s.C, "dbeta_out");
+  } else {
+    dgamma = at::empty({s.C}, fopt), dbeta = at::empty({s.C}, fopt);
+  }
+  Tensor dconv = empty_cl_bf16(s.N, s.C, s.H, s.W, dy), dres;
+  if (has_res) dres = empty_cl_bf16(s.N, s.C, s.H, s.W, dy);
+  const int Z = gn_splits(s.HW, s.C, s.G, 1);
+  Tensor ws = at::empty({(long)s.N * s.C * 2}, fopt), part;
+  if (Z > 1) part = at::empty({(long)s.N * Z * s.C * 2}, fopt);
+  launch_gn_bwd(dy.data_ptr(), y.data_ptr(), convout.data_ptr(),
+                gamma.data_ptr<float>(), mean.data_ptr<float>(),
+                rstd.data_ptr<float>(), dconv.data_ptr(),
+                has_res ? dres.data_ptr() : nullptr, ws.data_ptr<float>(),
+                Z > 1 ? part.data_ptr<float>() : nullptr,
+                dgamma.data_ptr<float>(), dbeta.data_ptr<float>(),
+                direct ? 1 : 0, s.N, s.HW, s.C, s.G, (int)act, st);
+  return {dconv, dres, dgamma, dbeta};
+}
+
+std::vector<Tensor> gn_bwd(Tensor dy, Tensor y, Tensor convout, Tensor gamma,
+                           Tensor mean, Tensor rstd, int64_t groups,
+                           int64_t act, bool has_res,
+                           c10::optional<Tensor> dgamma_out,
+                           c10::optional<Tensor> dbeta_out) {
+  check_cl(convout, "convout");
+  const GnShape s = check_gn(convout.size(0), convout.size(1), convout.size(2),
+                             convout.size(3), groups, "gn_bwd");
+  return gn_backward(dy, y, convout, gamma, mean, rstd, s, act, has_res,
+                     dgamma_out, dbeta_out, cur_stream());
+}
+
+// (forward, backward) GroupNorm kernel launches so far in this process.
+std::vector<int64_t> gn_launches() {
+  long f = 0, b = 0;
+  gn_launch_counts(&f, &b);
+  return {(int64_t)f, (int64_t)b};
+}
+
+void set_gn_split_hw_py(int64_t rows) { set_gn_split_hw((long)rows); }
+int64_t gn_split_hw_py() { return gn_split_hw(); }
+// row chunks per sample the forward / backward take at this shape
+int64_t gn_split_count(int64_t HW, int64_t C, int64_t groups, bool bwd) {
+  return gn_splits((int)HW, (int)C, (int)groups, bwd ? 1 : 0);
+}
+
+// Conv + GroupNorm [+ residual] [+ act]: the conv without a stats epilogue
+// (bf16 output, or split-K slabs the GroupNorm forward sums on read), then
+// the GroupNorm forward.  Returns [y, convout, mean, rstd].
+std::vector<Tensor> conv_gn_act_fwd(Tensor x, Tensor w, Tensor gamma,
+                                    Tensor beta, int64_t groups,
+                                    int64_t stride, int64_t pad, double eps,
+                                    int64_t act,
+                                    c10::optional<Tensor> residual) {
+  check_cl(x, "x");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 &&
+                  w.is_contiguous() && w.dim() == 4,
+              "w must be contiguous bf16 KRSC");
+  TORCH_CHECK(w.size(3) == x.size(1), "w in-channels mismatch");
+  const int K = (int)w.size(0);
+  ConvP p = make_convp(x, K, (int)w.size(1), (int)w.size(2), (int)stride,
+                       (int)pad);
+  const GnShape s = check_gn(p.Nb, K, p.Ho, p.Wo, groups, "conv_gn_act_fwd");
+  Tensor convout = empty_cl_bf16(p.Nb, K, p.Ho, p.Wo, x);
+  auto st = cur_stream();
+  int splitk = conv_fwd_splitk(p);
+  if (splitk > 1) {
+    int kchunk = ((p.Kd + splitk - 1) / splitk + 31) / 32 * 32;
+    splitk = (p.Kd + kchunk - 1) / kchunk;
+    Tensor ws = at::empty({(long)splitk * p.M * K},
+                          x.options().dtype(torch::kFloat32));
+    launch_conv_fwd_splitk(x.data_ptr(), w.data_ptr(), ws.data_ptr<float>(),
+                           p, splitk, st);
+    return gn_forward(convout, ws.data_ptr<float>(), splitk, s, gamma, beta,
+                      eps, act, residual, st);
+  }
+  launch_conv_fwd(x.data_ptr(), w.data_ptr(), convout.data_ptr(), nullptr, p,
+                  st);
+  return gn_forward(convout, nullptr, 0, s, gamma, beta, eps, act, residual,
+                    st);
+}
+
+// GroupNorm backward, then the weight gradient as conv_bn_act_bwd runs it
+// (direct flat-grad views, deferral), then dgrad.  No tap window is recorded:
+// a GN conv stays fully live in the optimizer's table.
+// Returns [dx, dw, dgamma, dbeta, dres].
+std::vector<Tensor> conv_gn_act_bwd(
+    Tensor dy, Tensor y, Tensor x, Tensor w, Tensor convout, Tensor gamma,
+    Tensor mean, Tensor rstd, int64_t groups, int64_t stride, int64_t pad,
+    int64_t act, bool need_dx, bool has_res, c10::optional<Tensor> dw_out,
+    c10::optional<Tensor> dgamma_out, c10::optional<Tensor> dbeta_out) {
+  check_cl(x, "x");
+  check_cl(convout, "convout");
+  const int K = (int)w.size(0), R = (int)w.size(1), S = (int)w.size(2);
+  ConvP p = make_convp(x, K, R, S, (int)stride, (int)pad);
+  const GnShape s = check_gn(p.Nb, K, p.Ho, p.Wo, groups, "conv_gn_act_bwd");
+  auto fopt = x.options().dtype(torch::kFloat32);
+  auto st = cur_stream();
+  const bool direct = dw_out.has_value();
+  TORCH_CHECK(direct == dgamma_out.has_value(),
+              "conv_gn_act_bwd: the gradient destinations are passed together");
+  auto g = gn_backward(dy, y, convout, gamma, mean, rstd, s, act, has_res,
+                       dgamma_out, dbeta_out, st);
+  const Tensor& dconv = g[0];
+  Tensor dw = direct ? *dw_out
+                     : at::zeros({(int64_t)K, R, S, (int64_t)p.C}, fopt);
+  if (direct && g_wgrad_defer) {
+    g_pending.push_back({x, dconv, dw, p});  // runs batched at flush_wgrad
+  } else {
+    int msplit = wgrad_msplit(p);
+    Tensor ws;
+    float* ws_ptr = nullptr;
+    if (msplit > 1) {
+      ws = at::empty({(long)msplit * K * p.Kd}, fopt);
+      ws_ptr = ws.data_ptr<float>();
+    }
+    launch_wgrad(x.data_ptr(), dconv.data_ptr(), dw.data_ptr<float>(), ws_ptr,
+                 p, (int)g_wgrad_tr, st);
+  }
+  Tensor dx;
+  if (need_dx)
+    dx = dgrad_dx(dconv, w, c10::nullopt, p, c10::nullopt, c10::nullopt, 0,
+                  st);
+  return {dx, dw, g[2], g[3], g[1]};
+}
+
 std::vector<Tensor> cross_entropy_fwd_bwd(Tensor logits, Tensor target) {
   check_f32(logits, "logits");
   TORCH_CHECK(target.scalar_type() == torch::kLong && target.is_contiguous());
@@ -1999,6 +2243,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("se_bwd", &se_bwd);
   m.def("se_launches", &se_launches);
   m.def("se_split_count", &se_split_count);
+  m.def("gn_fwd", &gn_fwd);
+  m.def("gn_bwd", &gn_bwd);
+  m.def("conv_gn_act_fwd", &conv_gn_act_fwd);
+  m.def("conv_gn_act_bwd", &conv_gn_act_bwd);
+  m.def("gn_launches", &gn_launches);
+  m.def("set_gn_split_hw", &set_gn_split_hw_py);
+  m.def("gn_split_hw", &gn_split_hw_py);
+  m.def("gn_split_count", &gn_split_count);
   m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.def("gemm_bf16", &gemm_bf16);
   m.def("adam_step", &adam_step);

@@ -393,6 +393,39 @@ void launch_se_bwd(const void* dy, const void* y, const void* u,
                    int splits, int act, int accum, hipStream_t st);
 void se_launch_counts(long* fwd, long* bwd);
 
+// gn_kernels.hip: GroupNorm.  x, res, y, dy, dconv, dres bf16 NHWC
+// [N][HW][C], 16-byte aligned; gamma, beta [C] f32 of any alignment; mean,
+// rstd [N][G] f32.  The caller (bind.cpp, check_gn) guarantees the domain:
+// C % 8 == 0, C <= 2048, C / G in {2, 4, 8, 16, 32, 64}, N <= 65535,
+// HW <= 2^20.
+// Rows per sample above which the two-launch split form runs
+// (HZ_GN_SPLIT_HW at load).
+void set_gn_split_hw(long rows);
+long gn_split_hw();
+// row chunks per sample of the forward (bwd = 0) or backward (bwd = 1) at
+// this shape; 1 = the one-launch form.  Never depends on the batch.
+int gn_splits(int HW, int C, int G, int bwd);
+// slabs == nullptr: x is the bf16 conv output and convout is not written.
+// Otherwise slabs [nsplit][N*HW][C] f32 (16-byte aligned) are summed in slab
+// order and convout receives the bf16 sum.  res may be nullptr; act: 0 none,
+// 1 ReLU, 2 ReLU6.  part: N * gn_splits(.., 0) * G * 2 floats, unused at one
+// split.  One launch, or two in the split form.
+void launch_gn_fwd(const void* x, const float* slabs, int nsplit,
+                   void* convout, const void* res, void* y,
+                   const float* gamma, const float* beta, float* mean,
+                   float* rstd, float* part, int N, int HW, int C, int G,
+                   float eps, int act, hipStream_t st);
+// The mask of `act` is taken from y.  dres may be nullptr.  ws: N * C * 2
+// floats, 16-byte aligned; part: N * gn_splits(.., 1) * C * 2 floats, unused
+// at one split.  accum != 0 adds dgamma, dbeta onto their destinations.
+// Two launches, or three in the split form.
+void launch_gn_bwd(const void* dy, const void* y, const void* x,
+                   const float* gamma, const float* mean, const float* rstd,
+                   void* dconv, void* dres, float* ws, float* part,
+                   float* dgamma, float* dbeta, int accum, int N, int HW,
+                   int C, int G, int act, hipStream_t st);
+void gn_launch_counts(long* fwd, long* bwd);
+
 // elem_kernels.hip: optimizers.  step_t is the device step counter; the
 // Adam launchers (and SGD with a table) increment it before the update.
 void launch_adam_step(float* master, float* grad, float* m, float* v,

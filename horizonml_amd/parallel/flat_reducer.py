@@ -143,7 +143,7 @@ def grad_units(model: torch.nn.Module):
     Units follow ``model.parameters()`` order, so each unit's params are a
     contiguous run of the flat buffer.
     """
-    from ..models.layers import (ConvBNAct, DepthwiseConvBNAct,
+    from ..models.layers import (ConvBNAct, ConvGNAct, DepthwiseConvBNAct,
                                  GroupedConvBNAct, Linear)
     from ..models.resnet import BasicBlock, Bottleneck
 
@@ -156,7 +156,7 @@ def grad_units(model: torch.nn.Module):
             return
         # (a grouped bottleneck runs per module: its convs are units)
         if isinstance(m, (ConvBNAct, DepthwiseConvBNAct, GroupedConvBNAct,
-                          Linear)):
+                          ConvGNAct, Linear)):
             units.append((m, list(m.parameters())))
             return
         for c in m.children():

@@ -14,7 +14,7 @@ from __future__ import annotations
 
 import torch.nn as nn
 
-from ..models.layers import ConvBNAct, SqueezeExcite
+from ..models.layers import ConvBNAct, ConvGNAct, SqueezeExcite
 from ..models.resnet import ResNet, resnet18
 from .tensor_parallel import ColumnParallelLinear, ShardedConvBNAct
 
@@ -24,6 +24,10 @@ def _shard_convs(module: nn.Module, world_size: int, rank: int, group):
         raise ValueError(
             "tp mode 'full' cannot shard a model with SqueezeExcite blocks: "
             "the gate needs every channel of an image on one rank")
+    if any(isinstance(m, ConvGNAct) for m in module.modules()):
+        raise ValueError(
+            "tp mode 'full' cannot shard a model with ConvGNAct layers: a "
+            "group's statistics need all of its channels on one rank")
     for name, child in module.named_children():
         if isinstance(child, ConvBNAct):
             if child.out_ch % world_size != 0:
