@@ -7,3 +7,4 @@ from .partition import partition_model, partition_units, split_counts  # noqa: F
 from .layers import (ConvBNAct, DepthwiseConvBNAct, GroupedConvBNAct,  # noqa: F401
                      ConvGNAct, Linear, GlobalAvgPool, MaxPool2d3x3s2, SqueezeExcite,
                      refresh_all_shadows)
+from .infer import fold_for_inference, unfold_inference  # noqa: F401

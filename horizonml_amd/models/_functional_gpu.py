@@ -13,6 +13,7 @@ from __future__ import annotations
 import torch
 
 from .. import ops as _ops
+from .layers import DepthwiseConvBNAct, fold_active
 
 
 def _C():
@@ -88,7 +89,26 @@ class ConvBNActFn(torch.autograd.Function):
                 dres if ctx.has_res else None, None)
 
 
+def _fold_route(*mods) -> bool:
+    """Folded-inference route (``models/infer.py``): every module folded and
+    in eval mode, and no graph being recorded.  ``fold_active`` is asked of
+    every module, so a training-mode call drops each stale fold."""
+    active = [fold_active(m) for m in mods]
+    return all(active) and not torch.is_grad_enabled()
+
+
+def _conv_folded(x, mod, residual=None):
+    """One launch: act(conv(x)·scale + bias (+ residual))."""
+    fn = (_C().dw_conv_affine_act_fwd if type(mod) is DepthwiseConvBNAct
+          else _C().conv_affine_act_fwd)
+    return fn(_cl(x), mod._shadow(), mod.fold_scale, mod.fold_bias,
+              mod.stride, mod.padding, mod.act,
+              None if residual is None else _cl(residual))
+
+
 def conv_bn_act(x, mod, residual=None):
+    if _fold_route(mod):
+        return _conv_folded(x, mod, residual)
     return ConvBNActFn.apply(x, mod.weight, mod.bn_weight, mod.bn_bias,
                              residual, mod)
 
@@ -126,6 +146,8 @@ class DwConvBNActFn(torch.autograd.Function):
 
 
 def dw_conv_bn_act(x, mod, residual=None):
+    if _fold_route(mod):
+        return _conv_folded(x, mod, residual)
     return DwConvBNActFn.apply(x, mod.weight, mod.bn_weight, mod.bn_bias,
                                residual, mod)
 
@@ -498,6 +520,14 @@ class ResBlockFn(torch.autograd.Function):
 
 
 def res_block(x, mods, ds_mod):
+    if _fold_route(*mods, *(() if ds_mod is None else (ds_mod,))):
+        # one launch per conv; the block's residual and final ReLU ride the
+        # last conv's epilogue
+        identity = x if ds_mod is None else _conv_folded(x, ds_mod)
+        h = x
+        for m in mods[:-1]:
+            h = _conv_folded(h, m)
+        return _conv_folded(h, mods[-1], identity)
     params = []
     for m in mods:
         params += [m.weight, m.bn_weight, m.bn_bias]

@@ -33,6 +33,39 @@ def _use_hip(x: torch.Tensor) -> bool:
     return x.is_cuda
 
 
+# -- folded inference (models/infer.py) -------------------------------------
+def drop_fold(mod: nn.Module):
+    """Remove the folded-BatchNorm constants of `mod`, if it carries any."""
+    if getattr(mod, "_folded", False):
+        mod._folded = False
+        del mod.fold_scale
+        del mod.fold_bias
+
+
+def fold_active(mod: nn.Module) -> bool:
+    """True when `mod` is folded and may use its constants.  A training-mode
+    call drops the fold instead: the running statistics are about to move,
+    so the constants must never be used again."""
+    if not getattr(mod, "_folded", False):
+        return False
+    if mod.training:
+        drop_fold(mod)
+        return False
+    return True
+
+
+def _affine_act(y, mod, residual):
+    """CPU form of the folded epilogue: ·scale + bias → (+res) → act."""
+    y = y * mod.fold_scale.view(1, -1, 1, 1) + mod.fold_bias.view(1, -1, 1, 1)
+    if residual is not None:
+        y = y + residual
+    if mod.act == 1:
+        y = F.relu(y)
+    elif mod.act == 2:
+        y = F.hardtanh(y, 0.0, 6.0)
+    return y
+
+
 class ConvBNAct(nn.Module):
     """Fused Conv2d + BatchNorm2d [+ residual add] [+ ReLU].
 
@@ -110,6 +143,8 @@ class ConvBNAct(nn.Module):
         # CPU reference path: torch ops, full autograd.
         w = self.weight.permute(0, 3, 1, 2)  # KRSC -> OIHW
         y = F.conv2d(x, w, None, stride=self.stride, padding=self.padding)
+        if fold_active(self):
+            return _affine_act(y, self, residual)
         y = F.batch_norm(y, self.running_mean, self.running_var,
                          self.bn_weight, self.bn_bias,
                          self.training, self.momentum, self.eps)
@@ -179,6 +214,8 @@ class DepthwiseConvBNAct(nn.Module):
         w = self.weight.permute(2, 0, 1).unsqueeze(1)
         y = F.conv2d(x, w, None, stride=self.stride, padding=self.padding,
                      groups=self.ch)
+        if fold_active(self):
+            return _affine_act(y, self, residual)
         y = F.batch_norm(y, self.running_mean, self.running_var,
                          self.bn_weight, self.bn_bias, self.training,
                          self.momentum, self.eps)

@@ -1631,6 +1631,90 @@ std::vector<Tensor> conv_gn_act_bwd(
   return {dx, dw, g[2], g[3], g[1]};
 }
 
+// ------------------------------------------------------ folded inference --
+// Eval-mode conv + BatchNorm folded to y = act(conv·scale + bias (+ res)):
+// one launch per conv (infer_kernels.hip), on the current stream, no
+// workspace and no host sync.  Everything is checked before the launch.
+void check_infer(const Tensor& scale, const Tensor& bias, int K, int64_t act,
+                 long M, long Mi, const c10::optional<Tensor>& residual,
+                 at::IntArrayRef out_shape) {
+  check_f32(scale, "scale");
+  check_f32(bias, "bias");
+  TORCH_CHECK(scale.dim() == 1 && scale.size(0) == K && bias.dim() == 1 &&
+                  bias.size(0) == K,
+              "scale and bias must be [", K, "]");
+  TORCH_CHECK(act >= 0 && act <= 2, "act must be 0, 1 or 2, got ", act);
+  TORCH_CHECK(M < (1L << 31) && Mi < (1L << 31),
+              "N*Ho*Wo and N*H*W must stay below 2^31");
+  if (residual.has_value()) {
+    check_cl(*residual, "residual");
+    TORCH_CHECK(residual->sizes() == out_shape,
+                "residual must have the output's shape");
+  }
+}
+
+Tensor conv_affine_act_fwd(Tensor x, Tensor w, Tensor scale, Tensor bias,
+                           int64_t stride, int64_t pad, int64_t act,
+                           c10::optional<Tensor> residual) {
+  check_cl(x, "x");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 &&
+                  w.is_contiguous() && w.dim() == 4,
+              "w must be contiguous bf16 KRSC");
+  TORCH_CHECK(w.size(3) == x.size(1), "w in-channels mismatch");
+  const int K = (int)w.size(0), R = (int)w.size(1), S = (int)w.size(2);
+  const long H = x.size(2), W = x.size(3);
+  TORCH_CHECK(stride >= 1 && pad >= 0 && H + 2 * pad >= R &&
+                  W + 2 * pad >= S,
+              "conv needs stride >= 1, pad >= 0 and an output of at least "
+              "1x1");
+  TORCH_CHECK(w.numel() < (1L << 31) && K <= (1 << 20),
+              "weight too large");
+  const long Ho = (H + 2 * pad - R) / stride + 1;
+  const long Wo = (W + 2 * pad - S) / stride + 1;
+  check_infer(scale, bias, K, act, x.size(0) * Ho * Wo, x.size(0) * H * W,
+              residual, {x.size(0), (int64_t)K, Ho, Wo});
+  const ConvP p = make_convp(x, K, R, S, (int)stride, (int)pad);
+  Tensor y = empty_cl_bf16(p.Nb, K, p.Ho, p.Wo, x);
+  launch_conv_infer(x.data_ptr(), w.data_ptr(), scale.data_ptr<float>(),
+                    bias.data_ptr<float>(), opt_ptr(residual), y.data_ptr(),
+                    p, (int)act, cur_stream());
+  return y;
+}
+
+Tensor dw_conv_affine_act_fwd(Tensor x, Tensor w, Tensor scale, Tensor bias,
+                              int64_t stride, int64_t pad, int64_t act,
+                              c10::optional<Tensor> residual) {
+  check_cl(x, "x");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == torch::kBFloat16 &&
+                  w.is_contiguous() && w.dim() == 3,
+              "w must be contiguous bf16 [R,S,C]");
+  const int Nb = (int)x.size(0), C = (int)x.size(1), H = (int)x.size(2),
+            W = (int)x.size(3);
+  const int R = (int)w.size(0), S = (int)w.size(1);
+  TORCH_CHECK((int)w.size(2) == C, "depthwise channel mismatch");
+  check_dw_geometry(R, S, stride, H, W, pad);
+  const int Ho = (H + 2 * (int)pad - R) / (int)stride + 1;
+  const int Wo = (W + 2 * (int)pad - S) / (int)stride + 1;
+  check_infer(scale, bias, C, act, (long)Nb * Ho * Wo, (long)Nb * H * W,
+              residual, {x.size(0), x.size(1), (int64_t)Ho, (int64_t)Wo});
+  Tensor y = empty_cl_bf16(Nb, C, Ho, Wo, x);
+  launch_dw_infer(x.data_ptr(), w.data_ptr(), scale.data_ptr<float>(),
+                  bias.data_ptr<float>(), opt_ptr(residual), y.data_ptr(), Nb,
+                  H, W, C, Ho, Wo, R, S, (int)stride, (int)pad, (int)act,
+                  cur_stream());
+  return y;
+}
+
+// [tile form, wave-split form, depthwise] folded-inference launches so far.
+std::vector<int64_t> infer_launches() {
+  long t = 0, s = 0, d = 0;
+  infer_launch_counts(&t, &s, &d);
+  return {(int64_t)t, (int64_t)s, (int64_t)d};
+}
+
+void set_infer_wsplit_py(int64_t mode) { set_infer_wsplit((int)mode); }
+int64_t infer_wsplit_py() { return infer_wsplit(); }
+
 std::vector<Tensor> cross_entropy_fwd_bwd(Tensor logits, Tensor target) {
   check_f32(logits, "logits");
   TORCH_CHECK(target.scalar_type() == torch::kLong && target.is_contiguous());
@@ -2251,6 +2335,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("set_gn_split_hw", &set_gn_split_hw_py);
   m.def("gn_split_hw", &gn_split_hw_py);
   m.def("gn_split_count", &gn_split_count);
+  m.def("conv_affine_act_fwd", &conv_affine_act_fwd, py::arg("x"),
+        py::arg("w"), py::arg("scale"), py::arg("bias"), py::arg("stride"),
+        py::arg("pad"), py::arg("act"), py::arg("residual") = py::none());
+  m.def("dw_conv_affine_act_fwd", &dw_conv_affine_act_fwd, py::arg("x"),
+        py::arg("w"), py::arg("scale"), py::arg("bias"), py::arg("stride"),
+        py::arg("pad"), py::arg("act"), py::arg("residual") = py::none());
+  m.def("infer_launches", &infer_launches);
+  m.def("set_infer_wsplit", &set_infer_wsplit_py);
+  m.def("infer_wsplit", &infer_wsplit_py);
   m.def("cross_entropy_fwd_bwd", &cross_entropy_fwd_bwd);
   m.def("gemm_bf16", &gemm_bf16);
   m.def("adam_step", &adam_step);

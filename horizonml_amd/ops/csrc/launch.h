@@ -426,6 +426,28 @@ void launch_gn_bwd(const void* dy, const void* y, const void* x,
                    int C, int G, int act, hipStream_t st);
 void gn_launch_counts(long* fwd, long* bwd);
 
+// infer_kernels.hip: folded-BatchNorm inference, one launch per conv:
+// y = act(conv(x, w)·scale[k] + bias[k] (+ res)).  x, res, y bf16 NHWC; scale,
+// bias f32 [K] of any alignment; res may be nullptr; act: 0 none, 1 ReLU,
+// 2 ReLU6.  The caller (bind.cpp, check_infer) guarantees Nb*Ho*Wo and
+// Nb*H*W below 2^31 and, for the depthwise form, w [R][S][C] with
+// R*S <= 25 (R = S = 3 or 5 keeps the taps in registers).
+// form of the dense kernel: -1 auto, 0 tile form only, 1 wave-split only
+// (HZ_INFER_WSPLIT at load)
+void set_infer_wsplit(int mode);
+int infer_wsplit();
+// 1 when the dense conv of geometry p runs in the wave-split form
+int infer_pick_wsplit(ConvP p);
+// p from make_convp: the clipped tap window is honoured
+void launch_conv_infer(const void* x, const void* w, const float* scale,
+                       const float* bias, const void* res, void* y, ConvP p,
+                       int act, hipStream_t st);
+void launch_dw_infer(const void* x, const void* w, const float* scale,
+                     const float* bias, const void* res, void* y, int Nb,
+                     int H, int W, int C, int Ho, int Wo, int R, int S,
+                     int str, int pad, int act, hipStream_t st);
+void infer_launch_counts(long* tile, long* wsplit, long* dw);
+
 // elem_kernels.hip: optimizers.  step_t is the device step counter; the
 // Adam launchers (and SGD with a table) increment it before the update.
 void launch_adam_step(float* master, float* grad, float* m, float* v,

@@ -21,10 +21,11 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 HIP_SOURCES = ["conv_kernels.hip", "elem_kernels.hip", "head_kernels.hip",
-               "grouped_kernels.hip", "se_kernels.hip", "gn_kernels.hip"]
+               "grouped_kernels.hip", "se_kernels.hip", "gn_kernels.hip",
+               "infer_kernels.hip"]
 HIPCC_FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
                "-ffast-math"]
-# per-file additions: head_, grouped_, se_ and gn_kernels.hip are compiled
+# per-file additions: head_, grouped_, se_, gn_ and infer_kernels.hip are compiled
 # without packed-f32 VALU ops as a whole (elem_kernels.hip marks single
 # kernels, HZ_NO_PK_F32)
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
@@ -33,6 +34,7 @@ HIPCC_FILE_FLAGS = {
     "grouped_kernels.hip": NO_PK_F32,
     "se_kernels.hip": NO_PK_F32,
     "gn_kernels.hip": NO_PK_F32,
+    "infer_kernels.hip": NO_PK_F32,
 }
 
 
